@@ -1,7 +1,12 @@
 """Benchmark: AMG V-cycle apply on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps, writes DIR/z.npy if asked and
+prints the line (V-cycles/s, ms_per_step and the description of what was
+timed).  --full adds every other measurement and check to the line: roofline
+blocks, C-ABI ingest rate, secondary configurations, CPU baseline, oracle parity.
 
 Step = one V-cycle (Multigrid::apply, reference multigrid.rs:469) of the
 smoothed-aggregation hierarchy of the 3-D 7-point Laplacian (config C2:
@@ -86,6 +91,28 @@ def measured_traffic(edge, problem):
         return None, None
     d = json.load(open(files[-1]))
     return d["hbm_bytes_per_launch"], os.path.relpath(files[-1], ROOT)
+
+
+DUMP_MAX_ELEMS = 4 << 20  # 32 MB of fp64 per array (--dump-outputs writes at most 64 MB in all)
+
+
+def dump_outputs(path, z):
+    """--dump-outputs DIR: DIR/z.npy (float64) = the vector the last timed V-cycle
+    wrote (z = M b, what a caller of Multigrid::apply receives): all of it up to
+    DUMP_MAX_ELEMS entries, else the entries at DUMP_MAX_ELEMS sorted indices drawn
+    without replacement by numpy's default_rng(42) -- the same entries in every
+    run of the same arguments.  z: a device or host vector in global row order."""
+    import numpy as np
+    import torch
+    n = z.shape[0]
+    if n > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(42).choice(n, size=DUMP_MAX_ELEMS, replace=False))
+        z = z[torch.as_tensor(idx, device=z.device)] if isinstance(z, torch.Tensor) else z[idx]
+    if isinstance(z, torch.Tensor):
+        z = z.cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "z.npy"), np.ascontiguousarray(z, dtype=np.float64))
+    log(f"--dump-outputs: {os.path.join(path, 'z.npy')} ({z.shape[0]} of {n} entries)")
 
 
 def spmv_bytes(nrows, ncols, nnz):
@@ -609,6 +636,51 @@ def run_single(args):
     torch.cuda.synchronize()
     t_wall = time.perf_counter() - t_wall0
     ms_per_cycle = e0.elapsed_time(e1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, z)
+
+    nnz = A.nnz
+    plan = mg.cycle_plan()
+    psum = plan_summary(plan)
+    if args.plan_out:
+        with open(args.plan_out, "w") as fh:
+            json.dump({"steps": args.steps, "plan": plan}, fh)
+    line = {
+        "metric": METRIC,
+        "value": round(1000.0 / ms_per_cycle, 3),
+        "unit": "V-cycles/s",
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_cycle, 4),
+        "higher_is_better": True,
+        "scaling": "none",
+        "scaling_note": "single GPU: the N = 1 base of bench.py's default weak series "
+                        "(256^3 rows per GPU fixed as N grows; --workload c4 gives the strong series)",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (device-generated operator, splitmix64 rhs seed 42)",
+    }
+    config = {"workload": workload_name(args, dims),
+              "levels": len(levels), "fine_rows": n, "fine_nnz": nnz,
+              "hierarchy": levels, "setup_s": round(setup_s, 2),
+              "wall_ms_per_step": round(1000 * t_wall / args.steps, 4),
+              "vcycle_algorithmic_GB": round(psum["bytes"] / 1e9, 3),
+              "vcycle_GBs": round(psum["bytes"] / (ms_per_cycle * 1e-3) / 1e9, 1),
+              "vcycle_csr_equivalent_GB": round(psum["csr_bytes"] / 1e9, 3),
+              "vcycle_plan": {"launches": psum["launches"],
+                              "source": "amg_multigrid_cycle_plan (the launches the library makes)",
+                              "per_level_GB": [round(d["bytes"] / 1e9, 4) for d in psum["per_level"]],
+                              "per_level_launches": [d["launches"] for d in psum["per_level"]],
+                              "per_level_kernels": [d["kernels"] for d in psum["per_level"]],
+                              "per_level_storage": level_storages(mg)},
+              "locality_renumbered_levels": [l for l in range(mg.levels()) if mg.reordered(l)],
+              "dense_tail": dense_tail_info(plan, levels),
+              "parallelism": "single GPU"}
+    if not args.full:
+        # a plain run: the headline figure and the description of what was timed
+        # (read back from the library, nothing measured); the rest is --full's
+        return dict(line, config=dict(config, full=False))
 
     # fine-level SpMV kernel (the one the V-cycle's fine smoothing/residual use),
     # timed with HIP events on the library stream
@@ -620,7 +692,6 @@ def run_single(args):
     for _ in range(3):
         Arun.apply(y, x)
     spmv_ms = time_kernel(lambda: Arun.apply(y, x), 20, stream)
-    nnz = A.nnz
     info = Arun.spmv_info()
     bytes_spmv = spmv_bytes_fmt(Arun)
     del Arun
@@ -678,13 +749,6 @@ def run_single(args):
     A.apply(r, z)
     torch.cuda.synchronize()
     rho1 = float(torch.linalg.norm(b - r) / torch.linalg.norm(b))
-    plan = mg.cycle_plan()
-    psum = plan_summary(plan)
-    storage_plan = level_storages(mg)
-    vbytes, vbytes_csr = psum["bytes"], psum["csr_bytes"]
-    if args.plan_out:
-        with open(args.plan_out, "w") as fh:
-            json.dump({"steps": args.steps, "plan": plan}, fh)
 
     # the cycle's fused fine-level launches timed on their own (roofline: the
     # dominant one -- the launch the V-cycle spends most time in)
@@ -708,7 +772,6 @@ def run_single(args):
     if args.problem == "7pt" and args.edge == 256 and not args.no_secondary:
         secondary = secondary_configs(fa, ctx, stream, args)
 
-    cycles_per_s = 1000.0 / ms_per_cycle
     # (C5 stand-in: the counter file covers 80^3 elements, windows of 4096, renumbering on)
     c5_default = args.problem == "elast" and args.permute == 4096 and args.reorder == 1
     traffic, traffic_src = measured_traffic(args.elements if c5_default else args.edge, args.problem)
@@ -742,45 +805,17 @@ def run_single(args):
                     "csr": csr_block, "general": general}
     else:
         roofline = dict(a0_set, fp64_values=fp64_values, csr=csr_block, general=general)
-    return {
-        "metric": METRIC,
-        "value": round(cycles_per_s, 3),
-        "unit": "V-cycles/s",
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_cycle, 4),
-        "higher_is_better": True,
-        "scaling": "none",
-        "scaling_note": "single GPU: the N = 1 base of bench.py's default weak series "
-                        "(256^3 rows per GPU fixed as N grows; --workload c4 gives the strong series)",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (device-generated operator, splitmix64 rhs seed 42)",
-        "config": {"workload": workload_name(args, dims),
-                   "levels": len(levels), "fine_rows": n, "fine_nnz": nnz,
-                   "hierarchy": levels, "setup_s": round(setup_s, 2),
-                   "wall_ms_per_step": round(1000 * t_wall / args.steps, 4),
-                   "vcycle_algorithmic_GB": round(vbytes / 1e9, 3),
-                   "vcycle_GBs": round(vbytes / (ms_per_cycle * 1e-3) / 1e9, 1),
-                   "vcycle_csr_equivalent_GB": round(vbytes_csr / 1e9, 3),
-                   "vcycle_plan": {"launches": psum["launches"],
-                                   "source": "amg_multigrid_cycle_plan (the launches the library makes)",
-                                   "per_level_GB": [round(d["bytes"] / 1e9, 4) for d in psum["per_level"]],
-                                   "per_level_launches": [d["launches"] for d in psum["per_level"]],
-                                   "per_level_kernels": [d["kernels"] for d in psum["per_level"]],
-                                   "per_level_storage": storage_plan},
-                   "rel_residual_after_1_cycle": rho1,
-                   "locality_renumbered_levels": [l for l in range(mg.levels()) if mg.reordered(l)],
-                   "abi_ingest": abi,
-                   "secondary": secondary,
-                   "dense_tail": dense_tail_info(plan, levels),
-                   "parallelism": "single GPU"},
-        "fine_spmv_gbs": round(achieved, 1),
-        "roofline": roofline,
-        "cpu_baseline": cpu,
-        "parity": parity,
-    }
+    full_config = {}
+    for k, v in config.items():  # the plain line's description, the measured entries in their places
+        if k == "locality_renumbered_levels":
+            full_config["rel_residual_after_1_cycle"] = rho1
+        if k == "dense_tail":
+            full_config["abi_ingest"] = abi
+            full_config["secondary"] = secondary
+        full_config[k] = v
+    full_config["full"] = True
+    return dict(line, config=full_config, fine_spmv_gbs=round(achieved, 1), roofline=roofline,
+                cpu_baseline=cpu, parity=parity)
 
 
 def dense_tail_info(plan, levels):
@@ -902,6 +937,39 @@ def run_dist(args, world, rank, local_rank):
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     el = float(tmax[0])
     ms_per_cycle = 1000.0 * el / args.steps
+    cycles_per_s = 1000.0 / ms_per_cycle
+    # the timed z gathered on rank 0 (--dump-outputs, and --full's parity checks)
+    zparts = None
+    if args.full or args.dump_outputs:
+        zparts = [None] * world if rank == 0 else None
+        dist.gather_object((r0, z.cpu().numpy()), zparts, dst=0)
+    if args.dump_outputs and rank == 0:
+        z_all = np.empty(A_rows_global)
+        for (p0, zp) in zparts:
+            z_all[p0:p0 + zp.shape[0]] = zp
+        dump_outputs(args.dump_outputs, z_all)
+        del z_all
+    extra = {"levels": nl, "level_plan_rank0": infos, "setup_s": round(setup_s, 2),
+             "agglomerate_rows": args.agglomerate,
+             "halo_overlap": not args.no_overlap,
+             "dist_graph": graph,
+             "local_storages_rank0": storages,
+             "vcycle_plan_rank0": {"launches": plan["launches"],
+                                   "source": "amg_dist_cycle_plan (the launches this rank makes)",
+                                   "halo_bytes": plan["halo_bytes"],
+                                   "per_level_halo_bytes": [d["halo_bytes"] for d in plan["per_level"]],
+                                   "per_level_exchanges": [d["exchanges"] for d in plan["per_level"]],
+                                   "per_level_GB": [round(d["bytes"] / 1e9, 4) for d in plan["per_level"]],
+                                   "per_level_kernels": [d["kernels"] for d in plan["per_level"]]},
+             "rccl": fa.rccl_library(),
+             "rccl_ranks": comm.nranks,
+             "full": args.full}
+    if not args.full:
+        # a plain run: the headline figure and the description of what was timed
+        out = dist_line(args, world, dims, strong, ms_per_cycle, cycles_per_s, None, None, None, None, None,
+                        extra=extra, roofline={})
+        dist.destroy_process_group()
+        return out if rank == 0 else None
 
     # local fine SpMV kernel on this rank (owned rows, [owned|ghost] columns)
     Al = dm.level_matrix(0, "A")
@@ -927,11 +995,8 @@ def run_dist(args, world, rank, local_rank):
     x = torch.zeros_like(b)
     it, hist = dm.stationary_solve(b, x, max_iter=K + 1, rel_tol=1e-300)
     hist = np.asarray(hist, np.float64)
-    zparts = [None] * world if rank == 0 else None
-    dist.gather_object((r0, z.cpu().numpy()), zparts, dst=0)
     ga = torch.tensor([achieved], dtype=torch.float64)
     dist.all_reduce(ga, op=dist.ReduceOp.MIN)
-    cycles_per_s = 1000.0 / ms_per_cycle
     # rank 0, while the other ranks wait: the same global problem on this one GPU
     # (the single-GPU cycle the distributed one must reproduce; at 512^3 also
     # the base of the C4 strong-scaling ratio), then the oracle on that hierarchy
@@ -960,23 +1025,8 @@ def run_dist(args, world, rank, local_rank):
                       "hierarchy on one GPU (single-GPU path, measured in this job by rank 0)",
               "mall_caveat": C4_MALL_CAVEAT}
     out = dist_line(args, world, dims, strong, ms_per_cycle, cycles_per_s, ratio, c4, single, cpu, parity,
-                    extra={"levels": nl, "level_plan_rank0": infos, "setup_s": round(setup_s, 2),
-                           "fine_spmv_with_halo_ms": round(halo_ms, 4),
-                           "rel_residual_after_1_cycle": float(hist[1]) if len(hist) > 1 else None,
-                           "agglomerate_rows": args.agglomerate,
-                           "halo_overlap": not args.no_overlap,
-                           "dist_graph": graph,
-                           "local_storages_rank0": storages,
-                           "vcycle_plan_rank0": {"launches": plan["launches"],
-                                                 "source": "amg_dist_cycle_plan (the launches this rank makes)",
-                                                 "halo_bytes": plan["halo_bytes"],
-                                                 "per_level_halo_bytes": [d["halo_bytes"] for d in plan["per_level"]],
-                                                 "per_level_exchanges": [d["exchanges"] for d in plan["per_level"]],
-                                                 "per_level_GB": [round(d["bytes"] / 1e9, 4)
-                                                                  for d in plan["per_level"]],
-                                                 "per_level_kernels": [d["kernels"] for d in plan["per_level"]]},
-                           "rccl": fa.rccl_library(),
-                           "rccl_ranks": comm.nranks},
+                    extra=dict(extra, fine_spmv_with_halo_ms=round(halo_ms, 4),
+                               rel_residual_after_1_cycle=float(hist[1]) if len(hist) > 1 else None),
                     roofline={"bound": "hbm", "achieved": round(float(ga[0]), 1), "peak": HBM_PEAK_GBS,
                               "unit": "GB/s", "frac": round(float(ga[0]) / HBM_PEAK_GBS, 4), "traffic": None,
                               "kernel": f"{al_info['kernel']} SpMV (SET) on the rank-local A_0 (min over ranks)",
@@ -1260,6 +1310,17 @@ def run_loopback(args):
     ranks(timed)
     torch.cuda.synchronize()
     ms = 1000.0 * (time.perf_counter() - tw) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch.cat(zs))
+    extra = {"levels": nl, "level_plan_rank0": infos, "setup_s": round(setup_s, 2),
+             "agglomerate_rows": args.agglomerate, "physical_gpus": 1,
+             "note": f"{N} virtual ranks on one GPU (loopback transport): value is not a "
+                     f"multi-GPU rate; the line rehearses the N-GPU line's fields",
+             "full": args.full}
+    if not args.full:
+        # a plain run: the rate alone (parity, CPU baseline and the one-GPU ratio are --full's)
+        return dist_line(args, N, dims, strong, ms, 1000.0 / ms, None, None, None, None, None,
+                         extra=extra, roofline={}, transport="loopback (device copies)")
     K = args.parity_cycles if args.parity_cycles is not None else (10 if n <= (1 << 25) else 5)
     xs = [torch.zeros_like(bb) for bb in bs]
     hists = ranks(lambda r: dms[r].stationary_solve(bs[r], xs[r], max_iter=K + 1, rel_tol=1e-300)[1])
@@ -1282,11 +1343,7 @@ def run_loopback(args):
               "what": "loopback rehearsal: N virtual ranks time-share one GPU (not a scaling figure)",
               "mall_caveat": C4_MALL_CAVEAT}
     return dist_line(args, N, dims, strong, ms, cps, ratio, c4, single, cpu, parity,
-                     extra={"levels": nl, "level_plan_rank0": infos, "setup_s": round(setup_s, 2),
-                            "rel_residual_after_1_cycle": float(hists[0][1]) if len(hists[0]) > 1 else None,
-                            "agglomerate_rows": args.agglomerate, "physical_gpus": 1,
-                            "note": f"{N} virtual ranks on one GPU (loopback transport): value is not a "
-                                    f"multi-GPU rate; the line rehearses the N-GPU line's fields"},
+                     extra=dict(extra, rel_residual_after_1_cycle=float(hists[0][1]) if len(hists[0]) > 1 else None),
                      roofline={}, transport="loopback (device copies)")
 
 
@@ -1385,6 +1442,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else the line can carry: "
+                         "the roofline blocks (fine SpMV, fused fine launches, general CSR), the C-ABI ingest "
+                         "rate, config.secondary (C3, C5 stand-in), the CPU baseline and the oracle parity; "
+                         "distributed: the one-GPU base of ratio_vs_1gpu, parity and the CPU baseline.  The "
+                         "--no-* options below trim a --full run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/z.npy (float64; above 4M rows a "
+                         "fixed seeded sample of its entries), for comparing two builds output for output")
     ap.add_argument("--edge", type=int, default=256, help="grid edge per GPU")
     ap.add_argument("--box", type=int, default=2)
     ap.add_argument("--smoother", default=None, choices=["jacobi", "l1", "sgs", "block"],
@@ -1446,6 +1512,8 @@ def main():
     ap.add_argument("--dist", action="store_true",
                     help="distributed path even at world size 1 (1-rank RCCL; a check of run_dist)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
     if args.agglomerate is None:
         args.agglomerate = 16384 * max(1, args.loopback, int(os.environ.get("WORLD_SIZE", "1")))
     if args.smoother is None:

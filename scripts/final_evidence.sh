@@ -13,14 +13,14 @@ mkdir -p "$O"
 HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 SKIP=${SKIP:-}
-[[ $SKIP == *bench* ]] || timeout -k 10 400 python3 bench.py > "$O/bench_stdout.log" 2> "$O/bench_stderr.log" || exit 1
+[[ $SKIP == *bench* ]] || timeout -k 10 400 python3 bench.py --full > "$O/bench_stdout.log" 2> "$O/bench_stderr.log" || exit 1
 echo "bench: $(tail -1 "$O/bench_stdout.log" | cut -c1-160)"
 [[ $SKIP == *prof* ]] || timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv \
-    -- python3 "$R/bench.py" > "$O/bench_prof_stdout.log" 2> "$O/bench_prof_stderr.log" || exit 1
+    -- python3 "$R/bench.py" --full > "$O/bench_prof_stdout.log" 2> "$O/bench_prof_stderr.log" || exit 1
 echo "bench under rocprofv3: $(tail -1 "$O/bench_prof_stdout.log" | cut -c1-160)"
-timeout -k 10 500 python3 bench.py --problem 27pt > "$O/c3_stdout.log" 2> "$O/c3_stderr.log" || exit 1
+timeout -k 10 500 python3 bench.py --full --problem 27pt > "$O/c3_stdout.log" 2> "$O/c3_stderr.log" || exit 1
 echo "c3: $(tail -1 "$O/c3_stdout.log" | cut -c1-160)"
-timeout -k 10 500 python3 bench.py --problem elast > "$O/c5_stdout.log" 2> "$O/c5_stderr.log" || exit 1
+timeout -k 10 500 python3 bench.py --full --problem elast > "$O/c5_stdout.log" 2> "$O/c5_stderr.log" || exit 1
 echo "c5: $(tail -1 "$O/c5_stdout.log" | cut -c1-160)"
-timeout -k 10 500 python3 bench.py --dist > "$O/dist1_stdout.log" 2> "$O/dist1_stderr.log" || exit 1
+timeout -k 10 500 python3 bench.py --full --dist > "$O/dist1_stdout.log" 2> "$O/dist1_stderr.log" || exit 1
 echo "dist1: $(tail -1 "$O/dist1_stdout.log" | cut -c1-160)"

@@ -4,14 +4,16 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 R=$(pwd)
+export O="$R/${OUT_DIR:-bench_out}"
+mkdir -p "$O"
 timeout -s KILL 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS \
-    --kernel-trace -d "$R/gpurun_out/pmc_gtc" -o run --output-format csv \
-    -- python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-general --no-abi > "$R/gpurun_out/pmc_gtc.log" 2>&1 || exit 1
+    --kernel-trace -d "$O/pmc_gtc" -o run --output-format csv \
+    -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-general --no-abi > "$O/pmc_gtc.log" 2>&1 || exit 1
 python3 - <<'PY'
-import csv, glob, collections
+import csv, glob, collections, os
 per = collections.defaultdict(lambda: collections.defaultdict(float))
 cnt = collections.Counter()
-for f in glob.glob("gpurun_out/pmc_gtc/**/*counter_collection.csv", recursive=True):
+for f in glob.glob(os.environ["O"] + "/pmc_gtc/**/*counter_collection.csv", recursive=True):
     seen = set()
     for r in csv.DictReader(open(f)):
         n = r["Kernel_Name"].split("(")[0]

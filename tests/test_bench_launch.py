@@ -81,3 +81,28 @@ def test_dist_line_per_rank_vs_256cubed_single():
     d1 = bench.dist_line(args, 2, (256, 256, 512), False, 5.0, 700.0, 1.9, None, {"vcycles_per_s": 760.0},
                          None, None, {}, {})
     assert d1["config"]["per_rank_vs_256cubed_single"] is None  # no 256^3 base measured
+
+
+def test_dump_outputs_is_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a vector up to DUMP_MAX_ELEMS entries is written whole, a
+    longer one as the same seeded, sorted sample of its entries in every run;
+    float64 either way, and the cap keeps the file below 64 MB."""
+    import numpy as np
+    import bench
+    assert 8 * bench.DUMP_MAX_ELEMS <= 64 * 10 ** 6
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    small = np.linspace(-1.0, 1.0, 1000)
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert np.array_equal(np.load(tmp_path / "s" / "z.npy"), small)
+    big = np.arange(50000, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "a"), big)
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    a, b = np.load(tmp_path / "a" / "z.npy"), np.load(tmp_path / "b" / "z.npy")
+    assert a.dtype == np.float64 and a.shape == (1000,)
+    assert np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[-1] < 50000  # distinct entries of big, in row order
+
+
+def test_steps_must_be_positive():
+    p = run_bench(["--gpus", "1", "--steps", "0", "--warmup", "0"], {}, timeout=120)
+    assert p.returncode == 2 and "--steps" in p.stderr

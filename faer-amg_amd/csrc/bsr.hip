@@ -332,10 +332,7 @@ __global__ __launch_bounds__(256) void spmv_bsr3l_kernel(BsrArgs a) {
 }
 
 static bool bsr_disabled() {
-    static const bool off = [] {
-        const char *e = getenv("FAMG_NO_BSR");
-        return e && e[0] == '1';
-    }();
+    static const bool off = env_is_one("FAMG_NO_BSR");
     return off;
 }
 
@@ -478,10 +475,7 @@ void spmv_bsr(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
     const int64_t s0 = seg < 0 ? 0 : m.bsr_seg_slc[seg];
     const int64_t s1 = seg < 0 ? m.bsr_slices : m.bsr_seg_slc[seg + 1];
     if (s1 <= s0) return;
-    static const int32_t jmask = [] {
-        const char *e = getenv("FAMG_BSR_DIAG");
-        return (e && e[0] == '1') ? 0 : -1;
-    }();
+    static const int32_t jmask = env_is_one("FAMG_BSR_DIAG") ? 0 : -1;
     BsrArgs a{m.bsr_data.get(), m.bsr_row0.get(), m.bsr_soff.get(), (int32_t)s0, (int32_t)(s1 - s0),
               BsrEpi{x, y, epi.b, epi.d, epi.dc, epi.dt, epi.y2}, jmask};
     const dim3 grid((unsigned)ceil_div(s1 - s0, 4)), block(256);

@@ -99,21 +99,20 @@ void export_plan(const std::vector<LaunchRec> &plan, amg_launch_rec *recs, int64
 
 namespace famg {
 static std::atomic<int64_t> g_flag_val[FLAG_COUNT] = {
-    {[] { const char *e = getenv("FAMG_FOLD_XSCS"); return (int64_t)(e && e[0] == '1'); }()},
-    {[] { const char *e = getenv("FAMG_DIA_DK"); return (int64_t)!(e && e[0] == '0'); }()},
+    {(int64_t)env_is_one("FAMG_FOLD_XSCS")},
+    {(int64_t)env_not_zero("FAMG_DIA_DK")},
     {[] {
-        const char *e = getenv("FAMG_VEC_WPR");
-        const int w = e ? atoi(e) : 0;
-        return (int64_t)((w == 1 || w == 2 || w == 4) ? w : 0);
+        const int64_t w = env_int("FAMG_VEC_WPR", 0);
+        return (w == 1 || w == 2 || w == 4) ? w : (int64_t)0;
     }()},
-    {[] { const char *e = getenv("FAMG_GTX_TIME"); return (int64_t)(e ? atoi(e) : 2); }()},
-    {[] { const char *e = getenv("FAMG_SGS27_MARCH"); return (int64_t)(e ? atoi(e) : 1); }()},
-    {[] { const char *e = getenv("FAMG_XS_PIPE"); return (int64_t)(e ? atoi(e) : 2); }()},
-    {[] { const char *e = getenv("FAMG_BSR_KERNEL"); return (int64_t)(e ? atoi(e) : 0); }()},
-    {[] { const char *e = getenv("FAMG_BSR_LONG"); return (int64_t)(e ? atoll(e) : 48); }()},
-    {[] { const char *e = getenv("FAMG_DIA7_RP"); return (int64_t)(e ? atoi(e) : 0); }()},
-    {[] { const char *e = getenv("FAMG_FINE_FUSE"); return (int64_t)(e ? atoi(e) : 1); }()},
-    {[] { const char *e = getenv("FAMG_DENSE_TAIL"); return (int64_t)(e ? atoll(e) : 4096); }()}};
+    {env_int("FAMG_GTX_TIME", 2)},
+    {env_int("FAMG_SGS27_MARCH", 1)},
+    {env_int("FAMG_XS_PIPE", 2)},
+    {env_int("FAMG_BSR_KERNEL", 0)},
+    {env_int("FAMG_BSR_LONG", 48)},
+    {env_int("FAMG_DIA7_RP", 0)},
+    {env_int("FAMG_FINE_FUSE", 1)},
+    {env_int("FAMG_DENSE_TAIL", 4096)}};
 static std::atomic<uint64_t> g_flag_gen{0};
 int64_t flag(FlagId f) { return g_flag_val[f].load(std::memory_order_relaxed); }
 void set_flag(FlagId f, int64_t v) {

@@ -10,6 +10,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -125,6 +126,26 @@ struct Ctx {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Environment switches (FAMG_*, listed in INTEGRATION.md): every site reads its
+// switch once, into a static const, through one of these.
+inline bool env_is_one(const char *name) {  // set, and its first character is '1'
+    const char *e = getenv(name);
+    return e && e[0] == '1';
+}
+inline bool env_not_zero(const char *name) {  // unset, or its first character is not '0'
+    const char *e = getenv(name);
+    return !(e && e[0] == '0');
+}
+inline int64_t env_int(const char *name, int64_t dflt) {
+    const char *e = getenv(name);
+    return e ? atoll(e) : dflt;
+}
+// switches told apart by another character: the first one (0: empty), -1 when unset
+inline int env_char(const char *name) {
+    const char *e = getenv(name);
+    return e ? (int)(unsigned char)e[0] : -1;
+}
+
 // Run-time A/B switches that change which kernels a cycle launches (bitwise
 // neutral).  Read once from the environment (FAMG_FOLD_XSCS, FAMG_DIA_DK,
 // FAMG_VEC_WPR) into these flags; amg_set_flag changes one and bumps
@@ -154,6 +175,15 @@ struct LaunchLog {
     int32_t level_base = 0;  // added to log_at's level (a distributed cycle's redundant tail)
 };
 extern thread_local LaunchLog *g_launch_log;
+// Sets this thread's recorder (nullptr: mutes it) until the scope ends, then
+// puts the previous one back -- also when a launch throws.
+struct LaunchLogScope {
+    LaunchLog *const saved = g_launch_log;
+    explicit LaunchLogScope(LaunchLog *log) { g_launch_log = log; }
+    ~LaunchLogScope() { g_launch_log = saved; }
+    LaunchLogScope(const LaunchLogScope &) = delete;
+    LaunchLogScope &operator=(const LaunchLogScope &) = delete;
+};
 inline void log_launch(const char *name, int32_t kernel, int32_t mode, int64_t rows, int64_t bytes,
                        int64_t csr_bytes = -1) {
     if (g_launch_log)

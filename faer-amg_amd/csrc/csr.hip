@@ -55,10 +55,7 @@ __global__ void k_narrow_rp(const int64_t *rp64, int32_t *rp32, int64_t n1) {
 // storage's SpMV against the CSR-stream kernel on a fixed vector; mismatching
 // rows are reported on stderr.
 static bool storage_check_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_CHECK_STORAGE");
-        return e && e[0] == '1';
-    }();
+    static const bool on = env_is_one("FAMG_CHECK_STORAGE");
     return on;
 }
 
@@ -100,9 +97,9 @@ static void storage_check(GpuCsr &m) {
 // one warm-up; true if the classes win).  Both sum every row in the same order:
 // the choice changes no result.
 static bool xscs_beats_dia(GpuCsr &m) {
-    const char *e = getenv("FAMG_XSCS_VS_DIA");
-    if (!e || !e[0]) return true;
-    if (e[0] != 't') return e[0] == '1';
+    const int e = env_char("FAMG_XSCS_VS_DIA");
+    if (e <= 0) return true;
+    if (e != 't') return e == '1';
     hipStream_t s = m.ctx->stream;
     DevBuf<double> x(m.ncols), y(m.nrows);
     FAMG_CHECK_HIP(hipMemsetAsync(x.get(), 0, m.ncols * sizeof(double), s));
@@ -221,10 +218,7 @@ bool grid_from_offsets(const std::vector<int64_t> &offs_in, int64_t n, int64_t *
 
 // FAMG_INFER_GRID=0: only explicit grid hints (generators, box hierarchy, amg_csr_set_grid)
 static bool infer_grid_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_INFER_GRID");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_not_zero("FAMG_INFER_GRID");
     return on;
 }
 

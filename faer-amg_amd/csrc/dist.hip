@@ -1016,14 +1016,10 @@ struct DistMultigridOp : LinOp {
         DevBuf<double> b(std::max<int64_t>(1, nrows)), z(std::max<int64_t>(1, nrows));
         vec_fill(b.get(), 1.0, nrows, ctx->stream);
         LaunchLog log;
-        g_launch_log = &log;
-        try {
+        {
+            LaunchLogScope scope(&log);
             apply_eager(z.get(), b.get());
-        } catch (...) {
-            g_launch_log = nullptr;
-            throw;
         }
-        g_launch_log = nullptr;
         FAMG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
         return log.recs;
     }

@@ -93,7 +93,7 @@ struct GpuCsr {
     // Row segments (SGS colors, halo boundary/interior): [seg_rows[g], seg_rows[g+1]).
     // Schedule blocks and SELL slices never straddle a segment.
     std::vector<int64_t> seg_rows, seg_blk, seg_slc;
-    // SELL-64 copy with compressed column indices (spmv.hip, "SELL storage"):
+    // SELL-64 copy with compressed column indices (sell.hip):
     // slice s holds rows [sell_row0[s], sell_row0[s+1]) (<= 64), one lane per
     // row, sell_soff[s+1]-sell_soff[s] entry steps; sell_desc[s] = byte offset/128
     // of its block in sell_data | column mode << 30; sell_base = one int32 per step.
@@ -106,12 +106,12 @@ struct GpuCsr {
     int64_t sell_mode_slices[3] = {0, 0, 0};  // slices per column mode (implicit, u16, i32)
     bool sell_paired = true;  // step-pair layout (16-B value loads); false: one step per 512-B row
     bool sell_short = false;  // coded slices of <= 4 steps in equal pairs (spmv_sell_short_kernel)
-    // value codes (spmv.hip "value codes"): 0 = fp64 values, else 4/8/16-bit codes
+    // value codes (sell.hip "value codes"): 0 = fp64 values, else 4/8/16-bit codes
     // into sell_vtab (sell_ntab distinct bit patterns, ascending)
     int sell_vbits = 0;
     int64_t sell_ntab = 0;
     DevBuf<double> sell_vtab;
-    // DIA codes (spmv.hip "DIA codes"): dia_cw words of codes per row for the
+    // DIA codes (dia.hip): dia_cw words of codes per row for the
     // dia_k diagonals dia_off (ascending); value table = sell_vtab
     DevBuf<uint32_t> dia_codes;
     DevBuf<double> dia_vtab;
@@ -299,6 +299,9 @@ int csr_value_table(const GpuCsr &m, std::vector<unsigned long long> &tab);
 // other_bytes; true if built (bsr.hip)
 bool build_bsr(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes);
 void build_sell(GpuCsr &m, const std::vector<int64_t> &rp);
+// DIA codes for rows [r0, r1) of m with the vb-bit value table tab; true if built (dia.hip)
+bool build_dia(GpuCsr &m, int vb, const std::vector<unsigned long long> &tab, const std::vector<int64_t> &rp,
+               int64_t r0, int64_t r1, const int32_t *rowid = nullptr);
 // DIA codes of a color-permuted SGS copy (diagonals col - rowid[p]); true if built
 bool build_dia_sgs(GpuCsr &m, const int32_t *rowid);
 void choose_kernel(GpuCsr &m);
@@ -346,6 +349,41 @@ bool spmm_compressed(const GpuCsr &m, const double *x, int64_t ldx, double *y, i
                      hipStream_t s);
 void spmv(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi,
           hipStream_t s, int64_t seg = -1);
+
+// What one spmv() call launches, resolved once (spmv_route, spmv.hip): spmv()
+// switches on it, the launch plan records it and the format's launcher reads its
+// sub-decisions from it -- none of them evaluates a dispatch condition again.
+enum SpmvRouteTo : int {
+    ROUTE_GTX, ROUTE_GTC, ROUTE_BSR, ROUTE_SCS, ROUTE_XS, ROUTE_SELLP, ROUTE_DIA_SGS, ROUTE_DIA, ROUTE_SELL,
+    ROUTE_VECTOR, ROUTE_STREAM
+};
+struct SpmvRoute {
+    SpmvRouteTo to = ROUTE_STREAM;    // the entry point
+    int kernel = SPMV_KERNEL_STREAM;  // the SpmvKernel and the name the plan records
+    const char *name = "csr-stream";
+    int64_t seg = -1, r0 = 0, r1 = 0;  // the segment and its rows [r0, r1)
+    int runs = 0;             // DIA: 9 = nine runs of three offsets, -1 = the 7-point pattern, 0 = neither
+    int pat = 0;              // DIA: the run-pattern kernel (33, 27), 0 = the generic kernels
+    bool cst = false;         // DIA: constant stencil, no codes read
+    bool sell_short = false;  // SELL: spmv_sell_short_kernel
+    bool dk = false;          // the coded diagonal is one value (epi.dk): d is not read
+    bool rc = false;          // RESID0 gathers d as 1-B codes, not 8-B values
+};
+SpmvRoute spmv_route(const GpuCsr &m, SpmvMode mode, const SpmvEpi &epi, int64_t seg);
+// the epilogue takes the one value of a coded diagonal (A/B switch FAMG_DIA_DK=0 /
+// amg_set_flag(1, 0): a constant coded diagonal is still read per row)
+inline bool epi_dconst(const SpmvEpi &epi) { return epi.dc && epi.dk != 0.0 && flag(FLAG_DIA_DK) != 0; }
+// sub-decisions the format files own (dia.hip, sell.hip, scs.hip)
+void dia_route(const GpuCsr &m, const SpmvEpi &epi, SpmvRoute &r);
+bool sell_takes_short(const GpuCsr &m, SpmvMode mode, int64_t seg);
+bool scs_takes_xscs(const GpuCsr &m, int64_t seg);
+void spmv_dia(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
+              const SpmvRoute &r);
+void spmv_dia_sgs(const GpuCsr &m, const double *x, double *y, const SpmvEpi &epi, hipStream_t s,
+                  const SpmvRoute &r);
+void spmv_sell(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
+               const SpmvRoute &r);
+void spmm_sell(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, hipStream_t s);
 void spmv_bsr(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
               int64_t seg);
 void spmv_scs(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
@@ -354,7 +392,7 @@ bool xs_supports(SpmvMode mode);
 // Y = A X over k columns on x-staged SELL (xsell.hip); false for other storages
 bool spmm_xs(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, hipStream_t s);
 // the constant 7-point DIA kernel with a one-value Jacobi diagonal takes m's
-// JACOBI / RESID0 launches (spmv.hip: no codes read, d = epi.dk)
+// JACOBI / RESID0 launches (dia.hip: no codes read, d = epi.dk)
 bool dia7_cst_dk(const GpuCsr &m, const SpmvEpi &epi);
 // fine.hip: the folded correction v = d f + P v_c and one Jacobi step on a
 // constant 7-point fine level as one marching kernel (out = the Jacobi result)

@@ -1039,10 +1039,7 @@ static int fine_rr2_occupancy(size_t dyn) {
 
 // FAMG_FINE_RR=1: the round-5 resid+restrict kernel (A/B timing)
 static bool fine_rr_v1() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_FINE_RR");
-        return e && e[0] == '1';
-    }();
+    static const bool on = env_is_one("FAMG_FINE_RR");
     return on;
 }
 
@@ -1069,10 +1066,7 @@ static void fine_rr2(const GpuCsr &A, const GpuCsr &R, const double *f, double d
     }
     a.dk = dk;
     for (int k = 0; k < 7; k++) a.cst[k] = A.dia_cst_v[k];
-    {
-        const char *e = getenv("FAMG_FINE_DBG");  // timing experiments only (results wrong)
-        a.dbg = e ? atoi(e) : 0;
-    }
+    a.dbg = (int)env_int("FAMG_FINE_DBG", 0);  // timing experiments only (results wrong)
     const int64_t ntxy = (int64_t)a.ntx * a.nty;
     // occupancy at a typical run length, then the run length for one round of workgroups
     const size_t dyn = (size_t)8 * R2_WS * a.nclass;
@@ -1120,10 +1114,7 @@ void fine_resid_restrict(const GpuCsr &A, const GpuCsr &R, const double *f, doub
     }
     a.dk = dk;
     for (int k = 0; k < 7; k++) a.cst[k] = A.dia_cst_v[k];
-    {
-        const char *e = getenv("FAMG_FINE_DBG");  // timing experiments only (results wrong)
-        a.dbg = e ? atoi(e) : 0;
-    }
+    a.dbg = (int)env_int("FAMG_FINE_DBG", 0);  // timing experiments only (results wrong)
     const int64_t ntxy = (int64_t)a.ntx * a.nty;
     // occupancy with the dictionary part of the dynamic LDS (the per-plane class
     // bytes are small), then the run length, then the exact dynamic size
@@ -1171,10 +1162,7 @@ static int fine_pj2_occupancy() {
 
 // FAMG_FINE_PJ=1: the round-5 interp+Jacobi kernel (A/B timing)
 static bool fine_pj_v1() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_FINE_PJ");
-        return e && e[0] == '1';
-    }();
+    static const bool on = env_is_one("FAMG_FINE_PJ");
     return on;
 }
 
@@ -1194,10 +1182,7 @@ static void fine_pj2(const GpuCsr &A, const GpuCsr &P, const double *vc, const d
     a.out = out;
     a.dk = dk;
     for (int k = 0; k < 7; k++) a.cst[k] = A.dia_cst_v[k];
-    {
-        const char *e = getenv("FAMG_FINE_DBG");  // timing experiments only (results wrong)
-        a.dbg = e ? atoi(e) : 0;
-    }
+    a.dbg = (int)env_int("FAMG_FINE_DBG", 0);  // timing experiments only (results wrong)
     const int64_t ntxy = (int64_t)a.ntx * a.nty;
     const int64_t want = (int64_t)fine_pj2_occupancy() * std::max(A.ctx ? A.ctx->num_cus : 256, 1);
     int jper = (int)std::max<int64_t>(2, ceil_div((int64_t)a.nz * ntxy, want));

@@ -469,10 +469,7 @@ void gtc_release(GpuCsr &m) {
 
 // FAMG_GTC=0: keep the finalize-time storage for R and P
 static bool gtc_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_GTC");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_not_zero("FAMG_GTC");
     return on;
 }
 
@@ -591,19 +588,13 @@ void attach_box_transfers(const GpuCsr &Af, const GpuCsr &Ac, GpuCsr &R, GpuCsr 
 
 // fine points per lane along z in the P kernel (FAMG_GTC_TZ=8: eight)
 static int gtc_tz() {
-    static const int v = [] {
-        const char *e = getenv("FAMG_GTC_TZ");
-        return (e && e[0] == '8') ? 8 : 4;
-    }();
+    static const int v = env_char("FAMG_GTC_TZ") == '8' ? 8 : 4;
     return v;
 }
 
 // coarse planes per R tile (FAMG_GTC_RTZ=4: four, two rows per lane)
 static int gtc_rtz() {
-    static const int v = [] {
-        const char *e = getenv("FAMG_GTC_RTZ");
-        return (e && e[0] == '4') ? 4 : 2;
-    }();
+    static const int v = env_char("FAMG_GTC_RTZ") == '4' ? 4 : 2;
     return v;
 }
 
@@ -628,19 +619,13 @@ static int gtc_march_occupancy(bool df, size_t dyn) {
 
 // FAMG_GTC_MARCH=0: R in tiles of two coarse planes instead of marching workgroups
 static bool gtc_march_r() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_GTC_MARCH");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_not_zero("FAMG_GTC_MARCH");
     return on;
 }
 
 bool gtc_supports(const GpuCsr &m, SpmvMode mode) {
     return m.gtc_r ? (mode == SPMV_SET || mode == SPMV_SETDF) : (mode == SPMV_SET || mode == SPMV_ADD || mode == SPMV_ADD0);
 }
-
-// A/B switch FAMG_DIA_DK=0 (shared with the DIA kernels): a constant coded d is read per row
-static bool gtc_dk_enabled() { return flag(FLAG_DIA_DK) != 0; }
 
 // The z-tiles [ta, tb) of a launch whose column windows [w0(t), w0(t) + wz) read
 // no ghost plane (planes [kz_lo, 0) and [kz_own, kz_hi)): they can run while the
@@ -682,7 +667,7 @@ void spmv_gtc(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
     a.d = epi.d;
     a.dc = epi.dc;
     a.dt = epi.dt;
-    a.dconst = epi.dc && epi.dk != 0.0 && gtc_dk_enabled();
+    a.dconst = epi_dconst(epi);
     a.dk = epi.dk;
     a.y2 = epi.y2;
     // the launch's z-tile range: all tiles, or (segments of a rank-local matrix)
@@ -760,7 +745,7 @@ void spmv_gtc(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
     default: fail(AMG_ERR_UNSUPPORTED, "grid-transfer P: unsupported SpMV epilogue");              \
     }
         // FAMG_GTC_NT=0: cached fine-vector streams (non-temporal: P_0 ADD0 75.3 -> 72.8 us)
-        static const bool nt = !(getenv("FAMG_GTC_NT") && getenv("FAMG_GTC_NT")[0] == '0');
+        static const bool nt = env_not_zero("FAMG_GTC_NT");
         if (nt) {
             if (tz == 8) { FAMG_GTCI(8, true) }
             else { FAMG_GTCI(4, true) }

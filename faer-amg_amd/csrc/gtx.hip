@@ -321,10 +321,7 @@ void gtx_release(GpuCsr &m) {
 // FAMG_GTX: 0 off; 1 (default) levels whose R/P the 8-bit grid-transfer classes
 // (gtc.hip) cannot take; 2 every box level (A/B against gtc on level 0)
 int gtx_mode() {
-    static const int v = [] {
-        const char *e = getenv("FAMG_GTX");
-        return e ? atoi(e) : 1;
-    }();
+    static const int v = (int)env_int("FAMG_GTX", 1);
     return v;
 }
 
@@ -447,10 +444,7 @@ bool gtx_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which) {
         // four fine planes per lane, or two where that leaves fewer than 1024 tiles
         // (P_2 of the 256^3 cycle: 256 workgroups of 4 planes cover the chip once and
         // leave its cold misses exposed; FAMG_GTX_PTZ=4 / 2 forces)
-        static const int ptz = [] {
-            const char *e = getenv("FAMG_GTX_PTZ");
-            return e ? atoi(e) : 0;
-        }();
+        static const int ptz = (int)env_int("FAMG_GTX_PTZ", 0);
         const int64_t tiles4 = ((rx + 31) / 32) * ((ry + 7) / 8) * ((n / (rx * ry) + 3) / 4);
         const int first = ptz == 2 || (ptz == 0 && tiles4 < 1024) ? 2 : 4;
         for (int tzc : {first, 2}) {
@@ -637,7 +631,7 @@ void spmv_gtx(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
     a.d = epi.d;
     a.dc = epi.dc;
     a.dt = epi.dt;
-    a.dconst = epi.dc && epi.dk != 0.0 && flag(FLAG_DIA_DK) != 0;
+    a.dconst = epi_dconst(epi);
     a.dk = epi.dk;
     a.y2 = epi.y2;
     a.ntx = (int)ceil_div(a.rx, a.tx);

@@ -342,10 +342,7 @@ void SgsOp::apply_in_place(double *rhs) {
 // coarsest levels (FAMG_COARSE_DENSE_MAX, default 8192 rows) take chol.hip's
 // envelope factor.
 static int64_t coarse_dense_max() {
-    static const int64_t v = [] {
-        const char *e = getenv("FAMG_COARSE_DENSE_MAX");
-        return e ? std::max<int64_t>(0, atoll(e)) : (int64_t)8192;
-    }();
+    static const int64_t v = std::max<int64_t>(0, env_int("FAMG_COARSE_DENSE_MAX", 8192));
     return v;
 }
 
@@ -483,10 +480,7 @@ void MultigridOp::ensure_workspace() {
 // kernel (P_0 of a box hierarchy: its d*b epilogue streams dc and b instead of
 // v, the same bytes); 1 -- every DIA level; 0 -- none
 static int fold_dia_mode() {
-    static const int v = [] {
-        const char *e = getenv("FAMG_FOLD_DIA");
-        return e ? (e[0] == '1' ? 1 : 0) : -1;
-    }();
+    static const int c = env_char("FAMG_FOLD_DIA"), v = c < 0 ? -1 : c == '1';
     return v;
 }
 
@@ -578,10 +572,7 @@ bool fold_level(const CsrOp *A, const DiagOp *D, const CsrOp *P, bool fold_zero_
 // entry (Jacobi ping-pong flips an even number of times: 2*steps).
 // FAMG_SETDF=0: the next level's first Jacobi step from zero as its own d*f pass
 bool setdf_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_SETDF");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_not_zero("FAMG_SETDF");
     return on;
 }
 
@@ -624,13 +615,13 @@ void MultigridOp::ensure_tail() {
     hipStream_t s = ctx->stream;
     // column j of M = the tail's v for f = e_j (eager launches, before any capture)
     DevBuf<double> Mt(n * n), e(n);
-    LaunchLog *saved = g_launch_log;
-    g_launch_log = nullptr;
-    for (int64_t j = 0; j < n; j++) {
-        unit_vector(e.get(), n, j, s);
-        cycle(l0, Mt.get() + j * n, e.get(), true, nullptr, false);
+    {
+        LaunchLogScope mute(nullptr);
+        for (int64_t j = 0; j < n; j++) {
+            unit_vector(e.get(), n, j, s);
+            cycle(l0, Mt.get() + j * n, e.get(), true, nullptr, false);
+        }
     }
-    g_launch_log = saved;
     tail_M_.resize(n * n);
     dense_transpose(Mt.get(), tail_M_.get(), n, s);
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
@@ -863,19 +854,15 @@ std::vector<LaunchRec> MultigridOp::cycle_plan() {
     DevBuf<double> b(std::max<int64_t>(1, n)), z(std::max<int64_t>(1, n));
     vec_fill(b.get(), 1.0, n, ctx->stream);
     LaunchLog log;
-    g_launch_log = &log;
-    try {
+    {
+        LaunchLogScope scope(&log);
         if (levels[0].permuted) {
             gather_fine(b.get(), ctx->stream);
             perm_scatter(z.get(), perm_v0_.get(), levels[0].perm.get(), n, ctx->stream);
         } else {
             cycle(0, z.get(), b.get(), true, z.get());
         }
-    } catch (...) {
-        g_launch_log = nullptr;
-        throw;
     }
-    g_launch_log = nullptr;
     FAMG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return log.recs;
 }

@@ -437,7 +437,7 @@ void MultigridOp::reorder_levels() {
             }
         }
         const int64_t orig_lines = slice_lines(rp, col, n, nullptr, nullptr);
-        if (getenv("FAMG_REORDER_LOG"))
+        if (env_char("FAMG_REORDER_LOG") >= 0)
             fprintf(stderr, "reorder level %zu: x lines per SpMV (64-row slices) stored %lld, rcm %lld, chosen %lld\n",
                     l,
                     (long long)orig_lines, (long long)rcm_lines, (long long)best);

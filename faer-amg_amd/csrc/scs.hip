@@ -377,26 +377,17 @@ __global__ __launch_bounds__(256) void spmv_xscs_kernel(XscsArgs a) {
 // offsets (A/B switch FAMG_SCS_LANES=0: no stencil classes for them)
 constexpr int64_t SCS_LANES_ROWS = 131072;
 static bool scs_lanes_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_SCS_LANES");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_not_zero("FAMG_SCS_LANES");
     return on;
 }
 
 static bool scs_rows_pref() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_SCS_ROWS");
-        return e && e[0] == '1';
-    }();
+    static const bool on = env_is_one("FAMG_SCS_ROWS");
     return on;
 }
 
 static bool scs_disabled() {
-    static const bool off = [] {
-        const char *e = getenv("FAMG_NO_SCS");
-        return e && e[0] == '1';
-    }();
+    static const bool off = env_is_one("FAMG_NO_SCS");
     return off;
 }
 
@@ -416,10 +407,7 @@ void scs_release(GpuCsr &m) {
 // A/B switch FAMG_XSCS=0: no x-staged stencil classes; FAMG_XSCS_TILE=tx,ty,tz
 // forces the tile
 static bool xscs_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_XSCS");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_not_zero("FAMG_XSCS");
     return on;
 }
 
@@ -630,7 +618,7 @@ static void spmv_xscs(const GpuCsr &m, const double *x, double *y, SpmvMode mode
 // classes reads the dictionary per lane (profiles/r03/ab_xscs_*.log).  The
 // tile changes no result (same sums in the same order).
 static void xscs_autotune(GpuCsr &m) {
-    if (getenv("FAMG_XSCS_TILE")) {
+    if (env_char("FAMG_XSCS_TILE") >= 0) {
         m.xscs_tile_src = TUNE_ENV;
         return;
     }
@@ -640,7 +628,7 @@ static void xscs_autotune(GpuCsr &m) {
     const TileKey key{nx, ny, nz, rx, ry, rz, (int)m.scs_kr, m.scs_nclass, m.rframe.on()};
     {
         int t[3];
-        if (getenv("FAMG_TUNE_RETIME") == nullptr && tune_tile_lookup(key, t)) {
+        if (env_char("FAMG_TUNE_RETIME") < 0 && tune_tile_lookup(key, t)) {
             xscs_set_tile(m, t);
             m.xscs_tile_src = TUNE_TABLE;
             tune_tile_record(key, t, TUNE_TABLE);
@@ -899,9 +887,12 @@ static void spmv_xscs(const GpuCsr &m, const double *x, double *y, SpmvMode mode
     FAMG_CHECK_HIP(hipGetLastError());
 }
 
+// the x-staged kernel takes the launch (a framed matrix: segments are z-tile ranges, not row ranges)
+bool scs_takes_xscs(const GpuCsr &m, int64_t seg) { return m.xscs && (seg < 0 || m.cframe.on()); }
+
 void spmv_scs(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
               int64_t seg) {
-    if (m.xscs && (seg < 0 || m.cframe.on())) {  // a framed matrix: segments are z-tile ranges, not row ranges
+    if (scs_takes_xscs(m, seg)) {
         spmv_xscs(m, x, y, mode, epi, s, seg);
         return;
     }

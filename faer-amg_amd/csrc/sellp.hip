@@ -168,10 +168,7 @@ __global__ __launch_bounds__(256) void spmv_sellp_kernel(SellpArgs a) {
 }
 
 static bool sellp_disabled() {
-    static const bool off = [] {
-        const char *e = getenv("FAMG_NO_SELLP");
-        return e && e[0] == '1';
-    }();
+    static const bool off = env_is_one("FAMG_NO_SELLP");
     return off;
 }
 
@@ -353,20 +350,13 @@ bool build_sellp(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes)
 
 // two code words per step group (A/B switch FAMG_SELLP_W1=1: one)
 static int sellp_w2_enabled() {
-    static const int on = [] {
-        const char *e = getenv("FAMG_SELLP_W1");
-        return (e && e[0] == '1') ? 0 : 1;
-    }();
+    static const int on = env_is_one("FAMG_SELLP_W1") ? 0 : 1;
     return on;
 }
 
 // slices per wave (A/B switch FAMG_SELLP_SPW=n, default 1)
 static int sellp_spw() {
-    static const int v = [] {
-        const char *e = getenv("FAMG_SELLP_SPW");
-        const int k = e ? atoi(e) : 1;
-        return k > 0 ? k : 1;
-    }();
+    static const int k = (int)env_int("FAMG_SELLP_SPW", 1), v = k > 0 ? k : 1;
     return v;
 }
 

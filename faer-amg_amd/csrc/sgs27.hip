@@ -438,53 +438,34 @@ __global__ __launch_bounds__(64 * NW) void k_sgs27_march(Sgs27Args a) {
 
 // FAMG_SGS_FUSED=0 (or amg_set_sgs_fused(0)): colour launches instead of the
 // fused phases; 2: four phases per step instead of three (A/B, tests)
-int g_sgs_fused = [] {
-    const char *e = getenv("FAMG_SGS_FUSED");
-    return (e && e[0] == '0') ? 0 : (e && e[0] == '2') ? 2 : 1;
-}();
+int g_sgs_fused = env_char("FAMG_SGS_FUSED") == '0' ? 0 : env_char("FAMG_SGS_FUSED") == '2' ? 2 : 1;
 static bool sgs_fused_enabled() { return g_sgs_fused != 0; }
 
 // rows per workgroup and independent points per lane (A/B switches
 // FAMG_SGS27_TY, FAMG_SGS27_U)
 static int sgs27_ty() {
-    static const int v = [] {
-        const char *e = getenv("FAMG_SGS27_TY");
-        const int t = e ? atoi(e) : 0;
-        return t >= 2 && t <= 64 ? t : 16;
-    }();
+    static const int t = (int)env_int("FAMG_SGS27_TY", 0), v = t >= 2 && t <= 64 ? t : 16;
     return v;
 }
 static int sgs27_u() {
-    static const int v = [] {
-        const char *e = getenv("FAMG_SGS27_U");
-        return (e && e[0] == '2') ? 2 : 1;
-    }();
+    static const int v = env_char("FAMG_SGS27_U") == '2' ? 2 : 1;
     return v;
 }
 // waves per workgroup (FAMG_SGS27_NW: 4 or 8)
 static int sgs27_nw() {
-    static const int v = [] {
-        const char *e = getenv("FAMG_SGS27_NW");
-        return (e && e[0] == '8') ? 8 : 4;
-    }();
+    static const int v = env_char("FAMG_SGS27_NW") == '8' ? 8 : 4;
     return v;
 }
 // FAMG_SGS27_CST=0: load every row's codes even for a constant stencil (A/B)
 static bool sgs27_cst() {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_SGS27_CST");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_not_zero("FAMG_SGS27_CST");
     return on;
 }
 // The other parity's rows in LDS too (1024-thread workgroups, one per CU):
 // rows of TY + 2 nst (own) + 2 (TY + 2 nst + 2) (planes z -+ 1) doubles of nx
 // within 160 KB.  Returns the TY used, 0 if it does not fit or FAMG_SGS27_OL=0.
 static int sgs27_ol_ty(int nx, int nst) {
-    static const bool on = [] {
-        const char *e = getenv("FAMG_SGS27_OL");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_not_zero("FAMG_SGS27_OL");
     if (!on) return 0;
     for (int ty : {16, 12, 8, 4})
         if ((size_t)(ty + 2 * nst + 1 + 2 * (ty + 2 * nst + 2)) * nx * sizeof(double) <= 160 * 1024) return ty;

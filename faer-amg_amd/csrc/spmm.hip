@@ -2,7 +2,7 @@
 // 8(f) f2: the k-wide applies of near-null smoothing and the error propagator,
 // adaptivity.rs:168-244,307-390, hierarchy.rs:219-226).
 //
-// The SELL-64 SpMM (spmv.hip) covers fp64-valued SELL; here the storages the
+// The SELL-64 SpMM (sell.hip) covers fp64-valued SELL; here the storages the
 // hierarchies actually use: DIA codes (constant-stencil operators, incl. the
 // 33- and 27-diagonal run patterns), stencil classes (structured Galerkin
 // levels) and 3x3 blocks (elasticity / C5).  Each kernel reads a row's matrix

@@ -552,10 +552,7 @@ __global__ __launch_bounds__(256) void k_xs_fill(const int64_t *rp, const int32_
 }
 
 static bool xs_disabled() {
-    static const bool off = [] {
-        const char *e = getenv("FAMG_XS");
-        return e && e[0] == '0';
-    }();
+    static const bool off = !env_not_zero("FAMG_XS");
     return off;
 }
 

@@ -112,31 +112,45 @@ amg_status amg_set_alloc_policy(int32_t policy);
  *      multigrid.rs:137-158) -------------------------------------------------- */
 
 /* Run-time switches (no reference counterpart; measured A/B paths, every
- * setting bitwise neutral): 0 = fold the zero-guess step on x-staged class
- * levels (default 0, env FAMG_FOLD_XSCS), 1 = read a constant coded Jacobi
- * diagonal as one scalar (default 1, env FAMG_DIA_DK), 2 = waves per row of the
- * wave-per-row kernel (0 auto = chosen per matrix at finalize, 1/2/4; env
- * FAMG_VEC_WPR), 3 = where the wide grid-transfer classes (gtx.hip) are kept:
- * 0 wherever they build, 1 where they beat the transfer operator's other storage
- * in a setup-time timing, 2 (default) on operators of >= 2^18 rows (env
- * FAMG_GTX_TIME), 4 = marching
- * 27-point SGS phases (sgs27.hip): 0 = one workgroup per tile and plane, 1 = auto
- * (about one workgroup per CU), n >= 2 = n planes per workgroup (default 1, env
- * FAMG_SGS27_MARCH), 5 = x-staged SELL kernel (xsell.hip): 2 = one burst of
- * loads per row group with LDS-DMA staging (default), 1 = software-pipelined
- * batches, 0 = the round-4 kernel (env FAMG_XS_PIPE), 6 = 3x3-block SpMV kernel
- * (bsr.hip): 0 = the round-2 kernel (default), 1 = node columns first, 4-step
- * batches, 2 = columns first, 2-step batches pipelined, 3 = 4-step pipelined
- * (env FAMG_BSR_KERNEL), 7 = 3x3-block matrices whose slices (64 node rows)
- * average at least this many block steps take the long-row kernel that loads
- * the next 8 steps' node columns ahead (default 48, env FAMG_BSR_LONG; -1
- * never), 8 = row pairs per lane of the constant 7-point DIA kernel: 0 auto
- * (default: 2 for SET, 1 for the cycle's epilogues), 1, 2 or 4 adjacent 512-row
- * blocks per workgroup (env FAMG_DIA7_RP), 9 = the fine level of a constant
- * 7-point box hierarchy as marching fused kernels (fine.hip): 0 = off, 1 = on
- * (default), n >= 2 = n planes per workgroup (env FAMG_FINE_FUSE).  Setting one
- * makes every multigrid re-capture its hipGraph at its next apply.  amg_get_flag
- * reads the current value. */
+ * setting bitwise neutral).  Each takes its initial value from the environment
+ * variable named.  Setting one makes every multigrid re-capture its hipGraph at
+ * its next apply.  amg_get_flag reads the current value.
+ *   flag 0  FAMG_FOLD_XSCS    fold the zero-guess step on x-staged class levels
+ *                             (default 0)
+ *   flag 1  FAMG_DIA_DK       read a constant coded Jacobi diagonal as one scalar
+ *                             (default 1)
+ *   flag 2  FAMG_VEC_WPR      waves per row of the wave-per-row kernel: 0 auto =
+ *                             chosen per matrix at finalize (default), 1/2/4
+ *   flag 3  FAMG_GTX_TIME     where the wide grid-transfer classes (gtx.hip) are
+ *                             kept: 0 wherever they build, 1 where they beat the
+ *                             transfer operator's other storage in a setup-time
+ *                             timing, 2 (default) on operators of >= 2^18 rows
+ *   flag 4  FAMG_SGS27_MARCH  marching 27-point SGS phases (sgs27.hip): 0 = one
+ *                             workgroup per tile and plane, 1 = auto (about one
+ *                             workgroup per CU, default), n >= 2 = n planes per
+ *                             workgroup
+ *   flag 5  FAMG_XS_PIPE      x-staged SELL kernel (xsell.hip): 2 = one burst of
+ *                             loads per row group with LDS-DMA staging (default),
+ *                             1 = software-pipelined batches, 0 = the round-4 kernel
+ *   flag 6  FAMG_BSR_KERNEL   3x3-block SpMV kernel (bsr.hip): 0 = the round-2
+ *                             kernel (default), 1 = node columns first, 4-step
+ *                             batches, 2 = columns first, 2-step batches pipelined,
+ *                             3 = 4-step pipelined
+ *   flag 7  FAMG_BSR_LONG     3x3-block matrices whose slices (64 node rows)
+ *                             average at least this many block steps take the
+ *                             long-row kernel that loads the next 8 steps' node
+ *                             columns ahead (default 48; -1 never)
+ *   flag 8  FAMG_DIA7_RP      row pairs per lane of the constant 7-point DIA
+ *                             kernel: 0 auto (default: 2 for SET, 1 for the cycle's
+ *                             epilogues), 1, 2 or 4 adjacent 512-row blocks per
+ *                             workgroup
+ *   flag 9  FAMG_FINE_FUSE    the fine level of a constant 7-point box hierarchy as
+ *                             marching fused kernels (fine.hip): 0 = off, 1 = on
+ *                             (default), n >= 2 = n planes per workgroup
+ *   flag 10 FAMG_DENSE_TAIL   the dense tail of a mu = 1 cycle: the first level
+ *                             1 <= l < L - 1 of at most this many rows and every
+ *                             coarser one run as one dense GEMV v = M f, M built
+ *                             once from the cycle itself (default 4096; 0 = off) */
 amg_status amg_set_flag(int32_t which, int64_t value);
 amg_status amg_get_flag(int32_t which, int64_t *value);
 /* Stencil-class storage of a CSR operator (structured Galerkin operators whose

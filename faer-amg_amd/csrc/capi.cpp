@@ -918,6 +918,96 @@ amg_status amg_sa_build_box(amg_linop *A, int64_t nx, int64_t ny, int64_t nz, in
     });
 }
 
+// ------------------------------------------------------- near-null search
+
+}  // extern "C"
+
+namespace {
+// An n x k block on the device for the length of a call: the caller's device block
+// itself, or a host block staged whole (leading dimension n) and copied back by store().
+struct StagedBlock {
+    Ctx &ctx;
+    double *host = nullptr, *dev = nullptr;
+    int64_t ld = 0, ldh = 0, n = 0, k = 0;
+    DevBuf<double> buf;
+    StagedBlock(Ctx &c, double *X, int64_t ldx, int64_t rows, int64_t cols, amg_mem mem) : ctx(c), n(rows), k(cols) {
+        FAMG_REQUIRE(mem == AMG_MEM_DEVICE || mem == AMG_MEM_HOST, AMG_ERR_INVALID, "bad amg_mem");
+        ctx.set_device();
+        if (mem == AMG_MEM_DEVICE) {
+            dev = X;
+            ld = ldx;
+            return;
+        }
+        host = X;
+        ldh = ldx;
+        ld = n;
+        buf.resize(n * k);
+        dev = buf.get();
+        FAMG_CHECK_HIP(hipMemcpy2DAsync(dev, n * sizeof(double), host, ldh * sizeof(double), n * sizeof(double), k,
+                                        hipMemcpyHostToDevice, ctx.stream));
+    }
+    void store() {
+        if (host)
+            FAMG_CHECK_HIP(hipMemcpy2DAsync(host, ldh * sizeof(double), dev, n * sizeof(double), n * sizeof(double), k,
+                                            hipMemcpyDeviceToHost, ctx.stream));
+        if (host) FAMG_CHECK_HIP(hipStreamSynchronize(ctx.stream));
+    }
+};
+
+// the argument checks every block entry point shares, before anything touches a device
+void check_block_args(const double *X, int64_t ld, int64_t n, int64_t k) {
+    FAMG_REQUIRE(k >= 1 && n >= 0, AMG_ERR_INVALID, "need k >= 1 columns and n >= 0 rows");
+    FAMG_REQUIRE(k <= QR_MAX_K, AMG_ERR_UNSUPPORTED, "blocks of more than 64 columns are not supported");
+    FAMG_REQUIRE(n >= k, AMG_ERR_DIM, "the block has fewer rows than columns");
+    FAMG_REQUIRE(ld >= n, AMG_ERR_INVALID, "leading dimension too small");
+    FAMG_REQUIRE(X, AMG_ERR_INVALID, "null block");
+}
+}  // namespace
+
+extern "C" {
+
+amg_status amg_thin_qr(amg_ctx *ctx, double *X, int64_t ld, int64_t n, int64_t k, double *R, amg_mem mem) {
+    return guard([&] {
+        check_block_args(X, ld, n, k);
+        FAMG_REQUIRE(ctx, AMG_ERR_INVALID, "null context");
+        StagedBlock B(ctx->ctx, X, ld, n, k, mem);
+        thin_qr(ctx->ctx, B.dev, B.ld, n, k, R);
+        B.store();
+    });
+}
+
+amg_status amg_smooth_vectors(amg_linop *A, amg_linop *pc, double *X, int64_t ld, int64_t k, int64_t iters,
+                              double *cfs, amg_mem mem) {
+    return guard([&] {
+        auto a = need_csr(A);
+        LinOp &m = need(pc);
+        check_block_args(X, ld, a->nrows, k);
+        StagedBlock B(*a->ctx, X, ld, a->nrows, k, mem);
+        smooth_vectors(*a, m, B.dev, B.ld, k, iters, cfs);
+        B.store();
+    });
+}
+
+amg_status amg_create_weights(const amg_linop *A, const double *X, int64_t ld, int64_t k, double *w, amg_mem mem) {
+    return guard([&] {
+        auto a = need_csr(A);
+        check_block_args(X, ld, a->nrows, k);
+        StagedBlock B(*a->ctx, const_cast<double *>(X), ld, a->nrows, k, mem);  // read only: never stored back
+        create_weights(*a, B.dev, B.ld, k, w);
+    });
+}
+
+amg_status amg_find_near_null(amg_linop *A, double *X, int64_t ld, int64_t k, int64_t iters, int64_t block_size,
+                              int64_t strength_depth, double *cfs, amg_mem mem) {
+    return guard([&] {
+        auto a = need_csr(A);
+        check_block_args(X, ld, a->nrows, k);
+        StagedBlock B(*a->ctx, X, ld, a->nrows, k, mem);
+        find_near_null(a, B.dev, B.ld, k, iters, block_size, strength_depth, cfs);
+        B.store();
+    });
+}
+
 // ------------------------------------------------------------ solve drivers
 
 }  // extern "C"

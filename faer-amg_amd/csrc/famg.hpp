@@ -778,4 +778,22 @@ struct SaLevelInfo {
 std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn, int64_t ld, int64_t k,
                                       const double *weights, const SaConfig &cfg, std::vector<SaLevelInfo> *info);
 
+// ------------------------------------------- near-null search (nearnull.hip)
+
+constexpr int64_t QR_MAX_K = 64;  // widest block of the thin QR
+// In-place thin QR of the column-major n x k device block X (CholeskyQR2 with a
+// shifted fallback); R (host, k x k column-major, positive diagonal) may be null.
+// Synchronises the context stream (the k x k factors are computed on the host).
+void thin_qr(Ctx &ctx, double *X, int64_t ld, int64_t n, int64_t k, double *R);
+// smooth_vector (adaptivity.rs:307-390) on the device block X (n x k): two QRs,
+// `iters` times X <- thinQ(X - pc(A X)); cfs (host, k; may be null) = the A-norm
+// convergence factor of every returned column
+void smooth_vectors(CsrOp &A, LinOp &pc, double *X, int64_t ld, int64_t k, int64_t iters, double *cfs);
+// create_weights (adaptivity.rs:434-443): w_c = 1 / (x_c^T A x_c), X on the device, w on the host
+void create_weights(CsrOp &A, const double *X, int64_t ld, int64_t k, double *w);
+// find_near_null (adaptivity.rs:264-305): X (device) holds the start block of both
+// stages and returns the stage-2 basis
+void find_near_null(const CsrPtr &A, double *X, int64_t ld, int64_t k, int64_t iters, int64_t block_size,
+                    int64_t strength_depth, double *cfs);
+
 }  // namespace famg

@@ -201,6 +201,10 @@ SIGNATURES = {
     "amg_halo_plan_remap": (i32, [vp, i64, vp, vp, vp, P(i64), P(i64)]),
     "amg_dist_first_redundant_level": (i32, [i64, vp, i64, P(i64)]),
     "amg_trace_mark": (i32, [vp, i32]),
+    "amg_thin_qr": (i32, [vp, vp, i64, i64, i64, vp, C.c_int]),
+    "amg_smooth_vectors": (i32, [vp, vp, vp, i64, i64, i64, vp, C.c_int]),
+    "amg_create_weights": (i32, [vp, vp, i64, i64, vp, C.c_int]),
+    "amg_find_near_null": (i32, [vp, vp, i64, i64, i64, i64, i64, vp, C.c_int]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -911,6 +915,85 @@ def constant_candidates(n, block_size):
     for c in range(block_size):
         nn[c::block_size, c] = 1.0
     return nn / np.sqrt(n // block_size)
+
+
+def _block_copy(X):
+    """A writable column-major copy of an n x k block (numpy or torch), same kind."""
+    try:
+        import torch
+        if isinstance(X, torch.Tensor):
+            if X.dim() == 1:
+                X = X[:, None]
+            return X.t().clone(memory_format=torch.contiguous_format).t()
+    except ImportError:
+        pass
+    X = np.asarray(X, np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    return np.array(X, order="F", copy=True)
+
+
+def thin_qr(ctx, X, in_place=False):
+    """Thin QR of a column-major n x k block, k <= 64 (amg_thin_qr; the search's
+    x.qr().compute_thin_Q(), adaptivity.rs:329): returns (Q, R), R a k x k numpy
+    array with a positive diagonal.  in_place: X itself is overwritten by Q."""
+    Q = X if in_place else _block_copy(X)
+    p, m, n, k, ld = _dptr(Q)
+    R = np.zeros((k, k), order="F")
+    with _ordered(ctx, m):
+        _ck(_lib.amg_thin_qr(ctx.h, p, ld, n, k, R.ctypes.data_as(vp), m))
+    return Q, R
+
+
+def smooth_vectors(A, pc, k=None, iters=50, seed=None, X0=None):
+    """smooth_vector (adaptivity.rs:307-390): `iters` error-propagation steps
+    X <- thinQ(X - pc(A X)) from the start block X0 (n x k, numpy or torch; left
+    unchanged), or from default_rng(seed).standard_normal((n, k)).  Returns
+    (X, cfs): the basis and the A-norm convergence factor of each column."""
+    if X0 is None:
+        if k is None:
+            raise ValueError("give k or a start block X0")
+        X = np.asfortranarray(np.random.default_rng(seed).standard_normal((A.nrows, k)))
+    else:
+        X = _block_copy(X0)
+    p, m, n, kk, ld = _dptr(X)
+    if n != A.nrows or (k is not None and k != kk):
+        raise ValueError("the start block must be nrows x k")
+    cfs = np.zeros(kk)
+    with _ordered(A.ctx, m):
+        _ck(_lib.amg_smooth_vectors(A.h, pc.h, p, ld, kk, iters, cfs.ctypes.data_as(vp), m))
+    return X, cfs
+
+
+def create_weights(A, X):
+    """create_weights (adaptivity.rs:434-443): 1 / (x_c^T A x_c) per column."""
+    if isinstance(X, np.ndarray):
+        X = _colmajor_host(X, A.nrows)
+    p, m, n, k, ld = _dptr(X)
+    if n != A.nrows:
+        raise ValueError("the block must have one row per matrix row")
+    w = np.zeros(k)
+    with _ordered(A.ctx, m):
+        _ck(_lib.amg_create_weights(A.h, p, ld, k, w.ctypes.data_as(vp), m))
+    return w
+
+
+def find_near_null(A, k, iters=50, seed=0, block_size=1, strength_depth=1, X0=None):
+    """find_near_null (adaptivity.rs:264-305): the two-stage search (L1, then a
+    BlockSmoother over the strength graph's aggregates) from the start block
+    default_rng(seed).standard_normal((n, k)) (or X0).  Returns (X, cfs) of stage 2."""
+    if X0 is None:
+        X = np.asfortranarray(np.random.default_rng(seed).standard_normal((A.nrows, k)))
+    else:
+        X = _block_copy(X0)
+    p, m, n, kk, ld = _dptr(X)
+    if n != A.nrows or kk != k:
+        raise ValueError("the start block must be nrows x k")
+    cfs = np.zeros(k)
+    with _ordered(A.ctx, m):
+        _ck(_lib.amg_find_near_null(A.h, p, ld, k, iters, block_size, strength_depth,
+                                    cfs.ctypes.data_as(vp), m))
+    return X, cfs
 
 
 def stationary_solve(A, M, b, x, max_iter=100, rel_tol=1e-8):

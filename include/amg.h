@@ -481,6 +481,46 @@ amg_status amg_block_jacobi_smooth(const amg_linop *A, const amg_linop *P, int64
                                    amg_linop **out);
 amg_status amg_nn_postprocess(const amg_linop *A, int64_t iters, double *x, int64_t ld, int64_t k);
 
+/* ---- near-null search (adaptivity.rs:264-390, 434-443) -------------------------
+ * From a bare SPD matrix to the candidates amg_sa_build takes, on the device.
+ * Blocks are column-major n x k with a leading dimension, 1 <= k <= 64
+ * (AMG_ERR_UNSUPPORTED above; AMG_ERR_DIM when n < k; AMG_ERR_INVALID when
+ * ld < n).  AMG_MEM_HOST blocks are staged whole through the device.  The C ABI
+ * carries no random number generator: the caller supplies the start block (the
+ * reference draws it from an unseeded rand::rng()), so results are reproducible,
+ * bitwise from call to call. */
+
+/* The thin QR of the search (`x.qr().compute_thin_Q()`, adaptivity.rs:329,349,353):
+ * X is overwritten by Q; R (host, k x k column-major, may be NULL) is upper
+ * triangular with a strictly positive diagonal.  CholeskyQR2 on the device (Gram
+ * matrix on the fp64 matrix cores, k x k Cholesky on the host, X <- X R^-1), with
+ * shifted passes when the Cholesky breaks down (kappa(X) beyond ~1e7);
+ * AMG_ERR_INVALID when X is rank deficient.  Synchronises the context stream. */
+amg_status amg_thin_qr(amg_ctx *ctx, double *X, int64_t ld, int64_t n, int64_t k, double *R, amg_mem mem);
+/* smooth_vector (adaptivity.rs:307-390): X <- thinQ(thinQ(X)); `iters` times
+ * X <- thinQ(X - pc(A X)) (ErrorPropogator + QR, :351-354); then per column w of X
+ * cfs[c] = sqrt(ev^T A ev) / sqrt(w^T A w), ev = w - pc(A w) (:367-382; cfs host,
+ * k entries, may be NULL).  A is a CSR operator (A X is one SpMM, the matrix
+ * streamed once per 8 columns); pc any preconditioning handle -- a Diag
+ * (Jacobi/L1/L2) runs as one fused k-wide update, every other kind is applied
+ * column by column. */
+amg_status amg_smooth_vectors(amg_linop *A, amg_linop *pc, double *X, int64_t ld, int64_t k, int64_t iters,
+                              double *cfs, amg_mem mem);
+/* create_weights (adaptivity.rs:434-443, examples/amg/main.rs:571-580):
+ * w[c] = 1 / (x_c^T A x_c) (w host, k entries); AMG_ERR_NOT_SPD when a quadratic
+ * form is <= 0. */
+amg_status amg_create_weights(const amg_linop *A, const double *X, int64_t ld, int64_t k, double *w, amg_mem mem);
+/* find_near_null (adaptivity.rs:264-305): stage 1 = amg_smooth_vectors with the L1
+ * diagonal on a copy of the start block X; weights = amg_create_weights of that
+ * basis; a BlockSmoother over amg_aggregate_mis(amg_strength_graph(A, basis,
+ * weights, strength_depth, block_size)) (the MIS aggregates stand in for the
+ * modularity partitioner, as in amg_sa_build); stage 2 = amg_smooth_vectors with
+ * that BlockSmoother from the same start block (the reference draws a fresh random
+ * block here).  X returns the stage-2 basis, cfs (host, k, may be NULL) its
+ * convergence factors. */
+amg_status amg_find_near_null(amg_linop *A, double *X, int64_t ld, int64_t k, int64_t iters, int64_t block_size,
+                              int64_t strength_depth, double *cfs, amg_mem mem);
+
 /* Level accessors of a multigrid: A_l, R_l, P_l (l < levels-1), smoother S_l.
  * Returned handles are new references. */
 amg_status amg_multigrid_get_level(const amg_linop *mg, int64_t level, amg_linop **A,

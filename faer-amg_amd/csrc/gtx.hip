@@ -456,7 +456,13 @@ bool gtx_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which) {
             }
         }
     } else {
-        static const int cands[][3] = {{16, 8, 4}, {16, 4, 4}, {16, 8, 2}, {16, 8, 1}, {16, 4, 1},
+        // (8 x 8 x 4 before 16 x 4 x 4: for the same 256 rows its window is the smaller one for
+        // every step range of 3 or more (R's least), and under R_1's steps {-2,..,3}^3 it is 38.4 KB against 41.5 KB --
+        // four workgroups share a CU's 160 KB of LDS instead of three, and R_1 of the 256^3
+        // cycle has four workgroups per CU: one round of resident workgroups instead of 3 + 1.
+        // Its waves are 8 x 8 rows of a plane instead of 16 x 4, class-uniform on an estimated
+        // 56 % of the 64^3 rows' tiles against 44 %.  C2 R_1 SETDF 29.9 -> 23.6 us)
+        static const int cands[][3] = {{16, 8, 4}, {8, 8, 4}, {16, 4, 4}, {16, 8, 2}, {16, 8, 1}, {16, 4, 1},
                                        {8, 4, 1},  {8, 2, 1},  {4, 2, 1}};
         for (const auto &c : cands) {
             const int w0 = 2 * c[0] - 1 + hi[0] - lo[0], w1 = 2 * c[1] - 1 + hi[1] - lo[1],

@@ -227,8 +227,13 @@ struct XscsArgs {
     float rwx, rwy, rtx, rty;
 };
 
+// Two rows per lane under 8-bit class ids (A_1 of the 256^3 cycle: 4096 workgroups, 16 per
+// CU, windows of ~14 KB) are bounded to 96 VGPRs, five waves per SIMD: the JACOBI epilogue
+// took 128 (four; C2 A_1 JACOBI 33.1 -> 31.1 us, no scratch; the other epilogues already fit).
+// 16-bit ids (A_2: 512 workgroups, two per CU) keep the registers: the same bound cost A_2's
+// JACOBI 19.4 -> 21.2 us; a bound of six waves (80 VGPRs) spills.
 template <int MODE, int IB, int RL>
-__global__ __launch_bounds__(256) void spmv_xscs_kernel(XscsArgs a) {
+__global__ __launch_bounds__(256, (RL == 2 && IB == 1) ? 5 : 1) void spmv_xscs_kernel(XscsArgs a) {
     extern __shared__ double win[];
     const int tid = threadIdx.x;
     const int t = a.tile0 + xcd_remap(blockIdx.x, gridDim.x);

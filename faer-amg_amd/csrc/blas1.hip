@@ -5,6 +5,8 @@
 // here on HBM-resident vectors.  Streaming element-wise kernels use 16-byte
 // (2 x fp64) accesses per lane; reductions are deterministic (fixed grid, fixed
 // tree) so repeated solves are bitwise reproducible.
+#include <algorithm>
+
 #include "famg.hpp"
 
 namespace famg {
@@ -223,6 +225,145 @@ void dense_gemv(const double *M, const double *x, double *out, int64_t n, hipStr
     log_launch("gemv", -1, -1, n, 8 * n * n + 16 * n);
     if (n % 2 == 0 && n >= 2) hipLaunchKernelGGL(k_gemv2, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, M, x, out, n);
     else hipLaunchKernelGGL(k_gemv, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, M, x, out, n);
+    FAMG_CHECK_HIP(hipGetLastError());
+}
+
+// Y = M X for up to 8 columns (column-major X, Y): one wave per row, M's row read
+// once per column group.  Each column sums in k_gemv2's order for even n (the same
+// lane split over 16-B pairs, a0 + a1, the xor butterfly) and in k_gemv's for odd
+// n, so every column is bitwise dense_gemv.  X columns need only 8-B alignment.
+typedef double gemv_dbl2u_t __attribute__((ext_vector_type(2), aligned(8)));
+template <int KB, bool EVEN>
+__global__ __launch_bounds__(256) void k_gemm_cols(const double *M, const double *X, int64_t ldx, double *Y,
+                                                   int64_t ldy, int64_t n) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= n) return;
+    const double *mr = M + row * n;
+    double acc[KB];
+    if constexpr (EVEN) {
+        double a0[KB], a1[KB];
+#pragma unroll
+        for (int c = 0; c < KB; c++) a0[c] = a1[c] = 0.0;
+        constexpr int U = 8;
+        for (int64_t j0 = 2 * lane; j0 < n; j0 += 128 * U) {
+            gemv_dbl2_t m[U];
+#pragma unroll
+            for (int u = 0; u < U; u++)
+                m[u] = __builtin_nontemporal_load(reinterpret_cast<const gemv_dbl2_t *>(mr + min(j0 + 128 * u, n - 2)));
+#pragma unroll
+            for (int c = 0; c < KB; c++) {
+                gemv_dbl2_t xx[U];
+#pragma unroll
+                for (int u = 0; u < U; u++)
+                    xx[u] = *reinterpret_cast<const gemv_dbl2u_t *>(X + c * ldx + min(j0 + 128 * u, n - 2));
+#pragma unroll
+                for (int u = 0; u < U; u++)
+                    if (j0 + 128 * u < n) {
+                        a0[c] = fma(m[u].x, xx[u].x, a0[c]);
+                        a1[c] = fma(m[u].y, xx[u].y, a1[c]);
+                    }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < KB; c++) acc[c] = a0[c] + a1[c];
+    } else {
+#pragma unroll
+        for (int c = 0; c < KB; c++) acc[c] = 0.0;
+        for (int64_t j = lane; j < n; j += 64) {
+            const double mv = mr[j];
+#pragma unroll
+            for (int c = 0; c < KB; c++) acc[c] = fma(mv, X[c * ldx + j], acc[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < KB; c++)
+        for (int off = 32; off > 0; off >>= 1) acc[c] += __shfl_xor(acc[c], off);
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < KB; c++) Y[row + c * ldy] = acc[c];
+    }
+}
+
+void dense_gemm_cols(const double *M, const double *X, int64_t ldx, double *Y, int64_t ldy, int64_t n, int64_t k,
+                     hipStream_t s) {
+    if (n <= 0 || k <= 0) return;
+    const dim3 grid((unsigned)ceil_div(n, 4)), block(256);
+    const bool even = n % 2 == 0 && n >= 2;
+    for (int64_t c0 = 0; c0 < k; c0 += 8) {
+        const int kb = (int)std::min<int64_t>(8, k - c0);
+        log_launch("gemm_cols", -1, -1, n, 8 * n * n + 16 * n * kb);
+        const double *xc = X + c0 * ldx;
+        double *yc = Y + c0 * ldy;
+#define FAMG_GEMM(KB)                                                                                   \
+    if (even) hipLaunchKernelGGL((k_gemm_cols<KB, true>), grid, block, 0, s, M, xc, ldx, yc, ldy, n);    \
+    else hipLaunchKernelGGL((k_gemm_cols<KB, false>), grid, block, 0, s, M, xc, ldx, yc, ldy, n)
+        switch (kb) {
+        case 1: FAMG_GEMM(1); break;
+        case 2: FAMG_GEMM(2); break;
+        case 3: FAMG_GEMM(3); break;
+        case 4: FAMG_GEMM(4); break;
+        case 5: FAMG_GEMM(5); break;
+        case 6: FAMG_GEMM(6); break;
+        case 7: FAMG_GEMM(7); break;
+        default: FAMG_GEMM(8); break;
+        }
+#undef FAMG_GEMM
+        FAMG_CHECK_HIP(hipGetLastError());
+    }
+}
+
+// ---------------------------------------------------- k-wide vector kernels
+// (the block V-cycle's counterparts of vec_mul / vec_sub / vec_add_inplace /
+// vec_copy: the same products, differences and sums per entry)
+
+__global__ __launch_bounds__(256) void k_mul_cols(double *out, int64_t ldo, const double *d, const double *a,
+                                                  int64_t lda, int64_t n, int k) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double di = d[i];
+    for (int c = 0; c < k; c++) out[i + c * ldo] = di * a[i + c * lda];
+}
+// OP 0: out = a - b, 1: out = a + b, 2: out = a
+template <int OP>
+__global__ __launch_bounds__(256) void k_ew_cols(double *out, int64_t ldo, const double *a, int64_t lda,
+                                                 const double *b, int64_t ldb, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c = blockIdx.y;
+    if (i >= n) return;
+    const double av = a[i + c * lda];
+    if constexpr (OP == 0) out[i + c * ldo] = av - b[i + c * ldb];
+    else if constexpr (OP == 1) out[i + c * ldo] = av + b[i + c * ldb];
+    else out[i + c * ldo] = av;
+}
+
+void vec_mul_cols(double *out, int64_t ldo, const double *d, const double *a, int64_t lda, int64_t n, int64_t k,
+                  hipStream_t s) {
+    if (n <= 0 || k <= 0) return;
+    log_launch("vec_mul_cols", -1, -1, n, 8 * n + 16 * n * k);
+    hipLaunchKernelGGL(k_mul_cols, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, out, ldo, d, a, lda, n, (int)k);
+    FAMG_CHECK_HIP(hipGetLastError());
+}
+void vec_sub_cols(double *out, int64_t ldo, const double *a, int64_t lda, const double *b, int64_t ldb, int64_t n,
+                  int64_t k, hipStream_t s) {
+    if (n <= 0 || k <= 0) return;
+    log_launch("vec_sub_cols", -1, -1, n, 24 * n * k);
+    hipLaunchKernelGGL(k_ew_cols<0>, dim3((unsigned)ceil_div(n, 256), (unsigned)k), dim3(256), 0, s, out, ldo, a, lda, b,
+                       ldb, n);
+    FAMG_CHECK_HIP(hipGetLastError());
+}
+void vec_add_cols(double *x, int64_t ldx, const double *y, int64_t ldy, int64_t n, int64_t k, hipStream_t s) {
+    if (n <= 0 || k <= 0) return;
+    log_launch("vec_add_cols", -1, -1, n, 24 * n * k);
+    hipLaunchKernelGGL(k_ew_cols<1>, dim3((unsigned)ceil_div(n, 256), (unsigned)k), dim3(256), 0, s, x, ldx, x, ldx, y,
+                       ldy, n);
+    FAMG_CHECK_HIP(hipGetLastError());
+}
+void vec_copy_cols(double *dst, int64_t ldd, const double *src, int64_t lds, int64_t n, int64_t k, hipStream_t s) {
+    if (n <= 0 || k <= 0) return;
+    log_launch("vec_copy_cols", -1, -1, n, 16 * n * k);
+    hipLaunchKernelGGL(k_ew_cols<2>, dim3((unsigned)ceil_div(n, 256), (unsigned)k), dim3(256), 0, s, dst, ldd, src, lds,
+                       nullptr, (int64_t)0, n);
     FAMG_CHECK_HIP(hipGetLastError());
 }
 

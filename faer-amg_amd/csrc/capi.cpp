@@ -8,6 +8,7 @@
 #include <string>
 
 #include "handles.hpp"
+#include "solve.hpp"
 
 using namespace famg;
 
@@ -112,7 +113,8 @@ static std::atomic<int64_t> g_flag_val[FLAG_COUNT] = {
     {env_int("FAMG_BSR_LONG", 48)},
     {env_int("FAMG_DIA7_RP", 0)},
     {env_int("FAMG_FINE_FUSE", 1)},
-    {env_int("FAMG_DENSE_TAIL", 4096)}};
+    {env_int("FAMG_DENSE_TAIL", 4096)},
+    {env_int("FAMG_BLOCK_CYCLE", 1)}};
 static std::atomic<uint64_t> g_flag_gen{0};
 int64_t flag(FlagId f) { return g_flag_val[f].load(std::memory_order_relaxed); }
 void set_flag(FlagId f, int64_t v) {
@@ -434,6 +436,23 @@ amg_status amg_csr_spmv_epilogue(const amg_linop *op, int32_t mode, const double
     });
 }
 
+amg_status amg_csr_spmm_epilogue(const amg_linop *op, int32_t mode, const double *X, int64_t ldx, double *Y,
+                                 int64_t ldy, const double *B, int64_t ldb, const double *d, int64_t k) {
+    return guard([&] {
+        FAMG_REQUIRE(k >= 0, AMG_ERR_INVALID, "negative column count");
+        FAMG_REQUIRE(mode >= SPMV_SET && mode <= SPMV_JACOBI, AMG_ERR_INVALID, "mode must be SET, ADD, RESID or JACOBI");
+        auto p = need_csr(op);
+        if (k == 0) return;
+        FAMG_REQUIRE(X && Y && X != Y, AMG_ERR_INVALID, "X and Y must be distinct device blocks");
+        FAMG_REQUIRE((mode != SPMV_RESID && mode != SPMV_JACOBI) || B, AMG_ERR_INVALID, "B required");
+        FAMG_REQUIRE(mode != SPMV_JACOBI || d, AMG_ERR_INVALID, "d required");
+        FAMG_REQUIRE(ldx >= p->ncols && ldy >= p->nrows && (!B || ldb >= p->nrows), AMG_ERR_INVALID,
+                     "leading dimension too small");
+        p->ctx->set_device();
+        spmm_epi(p->m, X, ldx, Y, ldy, k, (SpmvMode)mode, SpmmEpi{B, ldb, d}, p->ctx->stream);
+    });
+}
+
 amg_status amg_csr_download(const amg_linop *op, int64_t *rowptr, int64_t *colidx, double *vals) {
     return guard([&] {
         auto p = need_csr(op);
@@ -539,11 +558,47 @@ static bool csr_multi_apply(LinOp &o, double *out, int64_t ld_out, const double 
     return true;
 }
 
+// k > 1 columns of any operator through its apply_block (a multigrid or a Composite:
+// one block cycle, flag FLAG_BLOCK_CYCLE; kinds without an override: apply() per
+// column); host blocks are staged whole.  in_place (rhs == out, square operators): the
+// device block is copied to the staging buffer first.
+static bool block_multi_apply(LinOp &o, double *out, int64_t ld_out, const double *rhs, int64_t ld_rhs, int64_t k,
+                              amg_mem mem, bool in_place = false) {
+    if (k <= 1) return false;
+    FAMG_REQUIRE(out && rhs, AMG_ERR_INVALID, "null vector");
+    FAMG_REQUIRE(ld_out >= o.nrows && ld_rhs >= o.ncols, AMG_ERR_INVALID, "leading dimension too small");
+    Ctx &ctx = *o.ctx;
+    ctx.set_device();
+    amg_ctx *ac = ctx_of(o);
+    const int64_t m = std::max<int64_t>(1, o.nrows), n = std::max<int64_t>(1, o.ncols);
+    if (mem == AMG_MEM_DEVICE) {
+        if (!in_place) {
+            o.apply_block(out, ld_out, rhs, ld_rhs, k);
+            return true;
+        }
+        if (ac->stage_in.size() < (size_t)(n * k)) ac->stage_in.resize(n * k);
+        vec_copy_cols(ac->stage_in.get(), n, rhs, ld_rhs, o.ncols, k, ctx.stream);
+        o.apply_block(out, ld_out, ac->stage_in.get(), n, k);
+        return true;
+    }
+    FAMG_REQUIRE(mem == AMG_MEM_HOST, AMG_ERR_INVALID, "bad amg_mem");
+    if (ac->stage_in.size() < (size_t)(n * k)) ac->stage_in.resize(n * k);
+    if (ac->stage_out.size() < (size_t)(m * k)) ac->stage_out.resize(m * k);
+    FAMG_CHECK_HIP(hipMemcpy2DAsync(ac->stage_in.get(), n * sizeof(double), rhs, ld_rhs * sizeof(double),
+                                    o.ncols * sizeof(double), k, hipMemcpyHostToDevice, ctx.stream));
+    o.apply_block(ac->stage_out.get(), m, ac->stage_in.get(), n, k);
+    FAMG_CHECK_HIP(hipMemcpy2DAsync(out, ld_out * sizeof(double), ac->stage_out.get(), m * sizeof(double),
+                                    o.nrows * sizeof(double), k, hipMemcpyDeviceToHost, ctx.stream));
+    FAMG_CHECK_HIP(hipStreamSynchronize(ctx.stream));
+    return true;
+}
+
 amg_status amg_linop_apply(amg_linop *op, double *out, int64_t ld_out, const double *rhs,
                            int64_t ld_rhs, int64_t k, amg_mem mem) {
     return guard([&] {
         LinOp &o = need(op);
         if (csr_multi_apply(o, out, ld_out, rhs, ld_rhs, k, mem)) return;
+        if (block_multi_apply(o, out, ld_out, rhs, ld_rhs, k, mem)) return;
         for_columns(o, out, ld_out, rhs, ld_rhs, k, mem, o.nrows, o.ncols,
                     [&](double *y, const double *x) { o.apply(y, x); });
     });
@@ -562,6 +617,7 @@ amg_status amg_precond_apply_in_place(amg_linop *op, double *rhs, int64_t ld, in
     return guard([&] {
         LinOp &o = need(op);
         FAMG_REQUIRE(o.nrows == o.ncols, AMG_ERR_DIM, "apply_in_place needs a square operator");
+        if (k > 1 && rhs && ld >= o.nrows && block_multi_apply(o, rhs, ld, rhs, ld, k, mem, true)) return;
         if (mem == AMG_MEM_DEVICE) {
             o.ctx->set_device();
             FAMG_REQUIRE(k >= 0 && (k == 0 || rhs) && ld >= o.nrows, AMG_ERR_INVALID, "bad vector");
@@ -756,6 +812,7 @@ amg_status amg_multigrid_apply(amg_linop *mg, double *out, int64_t ld_out, const
                                int64_t ld_rhs, int64_t k, amg_mem mem) {
     return guard([&] {
         auto m = need_mg(mg);
+        if (block_multi_apply(*m, out, ld_out, rhs, ld_rhs, k, mem)) return;
         for_columns(*m, out, ld_out, rhs, ld_rhs, k, mem, m->nrows, m->ncols,
                     [&](double *y, const double *x) { m->apply(y, x); });
     });
@@ -767,6 +824,16 @@ amg_status amg_multigrid_cycle_plan(amg_linop *mg, amg_launch_rec *recs, int64_t
         FAMG_REQUIRE(count && cap >= 0, AMG_ERR_INVALID, "bad argument");
         m->ctx->set_device();
         export_plan(m->cycle_plan(), recs, cap, count);
+    });
+}
+
+amg_status amg_multigrid_block_plan(amg_linop *mg, int64_t k, amg_launch_rec *recs, int64_t cap, int64_t *count) {
+    return guard([&] {
+        FAMG_REQUIRE(count && cap >= 0, AMG_ERR_INVALID, "bad argument");
+        FAMG_REQUIRE(k >= 1, AMG_ERR_INVALID, "block plan: need k >= 1 columns");
+        auto m = need_mg(mg);
+        m->ctx->set_device();
+        export_plan(m->block_plan(k), recs, cap, count);
     });
 }
 
@@ -1005,6 +1072,82 @@ amg_status amg_find_near_null(amg_linop *A, double *X, int64_t ld, int64_t k, in
         StagedBlock B(*a->ctx, X, ld, a->nrows, k, mem);
         find_near_null(a, B.dev, B.ld, k, iters, block_size, strength_depth, cfs);
         B.store();
+    });
+}
+
+amg_status amg_adaptive_config_default(amg_adaptive_config *cfg) {
+    return guard([&] {
+        FAMG_REQUIRE(cfg, AMG_ERR_INVALID, "null config");
+        std::memset(cfg, 0, sizeof(*cfg));
+        const amg_status st = amg_sa_config_default(&cfg->sa);
+        FAMG_REQUIRE(st == AMG_OK, st, "amg_sa_config_default failed");
+        cfg->max_components = 5;  // AdaptiveConfig defaults (adaptivity.rs)
+        cfg->test_iters = 50;
+    });
+}
+
+// AdaptiveConfig::build (adaptivity.rs:55-165): host orchestration over find_near_null,
+// thin_qr, create_weights, sa_build, smooth_vectors and the Composite.
+amg_status amg_adaptive_build(amg_linop *A, const double *X0, int64_t ld, int64_t dim,
+                              const amg_adaptive_config *cfg, double *cfs_out, amg_linop **composite_out) {
+    return guard([&] {
+        // argument checks, before anything touches a device
+        FAMG_REQUIRE(dim >= 2, AMG_ERR_INVALID, "adaptive build: dim must be >= 2 (the constant and one searched column)");
+        FAMG_REQUIRE(dim <= QR_MAX_K, AMG_ERR_UNSUPPORTED, "adaptive build: dim above 64 is not supported");
+        FAMG_REQUIRE(cfg && X0 && composite_out, AMG_ERR_INVALID, "null argument");
+        FAMG_REQUIRE(cfg->max_components >= 1, AMG_ERR_INVALID, "adaptive build: max_components must be >= 1");
+        FAMG_REQUIRE(cfg->test_iters >= 0, AMG_ERR_INVALID, "adaptive build: negative test_iters");
+        auto a = need_csr(A);
+        const int64_t n = a->nrows;
+        FAMG_REQUIRE(a->nrows == a->ncols, AMG_ERR_DIM, "adaptive build: the matrix must be square");
+        FAMG_REQUIRE(ld >= n, AMG_ERR_INVALID, "leading dimension too small");
+        FAMG_REQUIRE(n >= dim, AMG_ERR_DIM, "the block has fewer rows than columns");
+        Ctx &ctx = *a->ctx;
+        ctx.set_device();
+        hipStream_t s = ctx.stream;
+        SaConfig c;
+        c.block_size = cfg->sa.block_size;
+        c.candidate_dimension = cfg->sa.candidate_dimension;
+        c.strength_depth = cfg->sa.strength_depth;
+        c.smoothing_steps = cfg->sa.smoothing_steps;
+        c.coarsest_dim = cfg->sa.coarsest_dim;
+        c.max_levels = cfg->sa.max_levels;
+        c.omega = cfg->sa.omega;
+        c.smoother = cfg->sa.smoother;
+        DevBuf<double> X(n * dim);
+        std::vector<double> basis(n * dim), w(dim);
+        auto upload_x0 = [&] {
+            FAMG_CHECK_HIP(hipMemcpy2DAsync(X.get(), n * sizeof(double), X0, ld * sizeof(double), n * sizeof(double),
+                                            dim, hipMemcpyHostToDevice, s));
+        };
+        auto download = [&] {
+            FAMG_CHECK_HIP(hipMemcpyAsync(basis.data(), X.get(), n * dim * sizeof(double), hipMemcpyDeviceToHost, s));
+            FAMG_CHECK_HIP(hipStreamSynchronize(s));
+        };
+        // 1. (:56-70) the search on columns 1..dim-1, the constant in column 0, QR, weights
+        upload_x0();
+        find_near_null(a, X.get() + n, n, dim - 1, cfg->test_iters, c.block_size, c.strength_depth, nullptr);
+        vec_fill(X.get(), 1.0, n, s);
+        thin_qr(ctx, X.get(), n, n, dim, nullptr);
+        create_weights(*a, X.get(), n, dim, w.data());
+        download();
+        // 2. (:108-115) the first hierarchy and the composite over it
+        auto comp = std::make_shared<CompositeOp>();
+        comp->ctx = a->ctx;
+        comp->A = a;
+        comp->nrows = comp->ncols = n;
+        comp->comps.push_back(sa_build(a, basis.data(), n, dim, w.data(), c, nullptr));
+        // 3. (:117-162) search with the composite built so far, build, push
+        for (int64_t m = 1; m < cfg->max_components; m++) {
+            upload_x0();
+            smooth_vectors(*a, *comp, X.get(), n, dim, cfg->test_iters / (2 * m - 1), w.data());
+            if (cfs_out) std::memcpy(cfs_out + (m - 1) * dim, w.data(), dim * sizeof(double));
+            download();
+            auto next = sa_build(a, basis.data(), n, dim, w.data(), c, nullptr);  // weights = the factors
+            std::lock_guard<std::mutex> lk(comp->mtx);
+            comp->comps.push_back(next);
+        }
+        *composite_out = box(comp);
     });
 }
 

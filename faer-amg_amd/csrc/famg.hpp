@@ -349,6 +349,36 @@ bool spmm_compressed(const GpuCsr &m, const double *x, int64_t ldx, double *y, i
                      hipStream_t s);
 void spmv(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi,
           hipStream_t s, int64_t seg = -1);
+// The k-wide SpMV epilogues of the block V-cycle: B column-major with ldb, d one
+// diagonal shared by all columns.
+struct SpmmEpi {
+    const double *b = nullptr;
+    int64_t ldb = 0;
+    const double *d = nullptr;
+};
+// Y = A X (SET), Y += A X (ADD), Y = B - A X (RESID), Y = X + d (B - A X) (JACOBI)
+// over k columns; every column bitwise spmv(mode) of that column.  Storages with an
+// SpMM kernel (DIA codes, stencil classes, 3x3 blocks, pattern SELL, fp64 SELL-64,
+// x-staged SELL) read the matrix once per 8 columns with the epilogue fused at the
+// store; CSR-stream, value-coded SELL-64 and the 8-bit grid-transfer classes run
+// their single-vector row sums over 8 columns per launch; wave-per-row and the
+// wide grid-transfer classes run spmv(mode) per column.
+void spmm_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
+              const SpmmEpi &epi, hipStream_t s);
+// m's storage has an SpMM kernel (what spmm / spmm_epi launch once per 8 columns)
+bool spmm_has_kernel(const GpuCsr &m);
+bool spmm_compressed_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k,
+                         SpmvMode mode, const SpmmEpi &epi, hipStream_t s);
+void spmm_sell_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
+                   const SpmmEpi &epi, hipStream_t s);
+// value-coded SELL-64 (sell.hip) and the 8-bit grid-transfer classes (gtc.hip; SET, and ADD
+// for P) over 8 columns per launch: the single-vector kernels' row sums per column
+void spmm_sell_coded(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
+                     const SpmmEpi &epi, hipStream_t s);
+void spmm_gtc(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
+              hipStream_t s);
+bool spmm_xs_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
+                 const SpmmEpi &epi, hipStream_t s);
 
 // What one spmv() call launches, resolved once (spmv_route, spmv.hip): spmv()
 // switches on it, the launch plan records it and the format's launcher reads its
@@ -450,6 +480,18 @@ void trace_mark(Ctx &ctx, int32_t tag);
 
 // dense row-major GEMV: out = M * x (M n x n)
 void dense_gemv(const double *M, const double *x, double *out, int64_t n, hipStream_t s);
+// Y = M X over k columns (column-major X, Y): M's rows read once per 8 columns,
+// every column bitwise dense_gemv
+void dense_gemm_cols(const double *M, const double *X, int64_t ldx, double *Y, int64_t ldy, int64_t n, int64_t k,
+                     hipStream_t s);
+// k-wide element-wise kernels of the block V-cycle (column-major blocks): out = d * a
+// (one diagonal for all columns), out = a - b, x += y, dst = src
+void vec_mul_cols(double *out, int64_t ldo, const double *d, const double *a, int64_t lda, int64_t n, int64_t k,
+                  hipStream_t s);
+void vec_sub_cols(double *out, int64_t ldo, const double *a, int64_t lda, const double *b, int64_t ldb, int64_t n,
+                  int64_t k, hipStream_t s);
+void vec_add_cols(double *x, int64_t ldx, const double *y, int64_t ldy, int64_t n, int64_t k, hipStream_t s);
+void vec_copy_cols(double *dst, int64_t ldd, const double *src, int64_t lds, int64_t n, int64_t k, hipStream_t s);
 // RCM node order (new -> old) of the node graph of an n x n CSR, bs dofs per node (reorder.hip)
 std::vector<int32_t> rcm_order(const std::vector<int64_t> &rp, const std::vector<int32_t> &col, int64_t n, int bs);
 
@@ -491,6 +533,10 @@ struct LinOp : std::enable_shared_from_this<LinOp> {
     virtual Kind kind() const = 0;
     // LinOp::apply -- out = M rhs (device, one column), out overwritten.
     virtual void apply(double *out, const double *rhs) = 0;
+    // out = M rhs over k columns (column-major device blocks, leading dimensions
+    // ldo / ldr; out != rhs).  Default: apply() column by column.  Every override
+    // computes each column bitwise as apply() does.
+    virtual void apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k);
     // BiLinOp::transpose_apply -- symmetric operators reuse apply.
     virtual void transpose_apply(double *out, const double *rhs) { apply(out, rhs); }
     // Precond::apply_in_place -- default: copy to scratch, then apply.
@@ -508,6 +554,7 @@ struct CsrOp : LinOp {
     std::shared_ptr<CsrOp> transpose_;  // lazy, for transpose_apply
     Kind kind() const override { return Kind::Csr; }
     void apply(double *out, const double *rhs) override;
+    void apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) override;  // one SpMM
     void transpose_apply(double *out, const double *rhs) override;
     const double *diagonal();
 };
@@ -524,6 +571,7 @@ struct DiagOp : LinOp {
     Kind kind() const override { return Kind::Diag; }
     bool is_precond() const override { return true; }
     void apply(double *out, const double *rhs) override;
+    void apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) override;  // one k-wide scale
     void apply_in_place(double *rhs) override;
 };
 
@@ -569,6 +617,8 @@ struct CoarseCholOp : LinOp {
     Kind kind() const override { return Kind::Coarse; }
     bool is_precond() const override { return true; }
     void apply(double *out, const double *rhs) override;
+    // the dense inverse as dense_gemm_cols; the envelope factor column by column
+    void apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) override;
 };
 
 struct MgLevel {
@@ -584,7 +634,11 @@ struct MgLevel {
     const LinOpPtr &origP() const { return oP ? oP : P; }
     // device workspaces (allocated lazily at first apply)
     DevBuf<double> v, f, t, r;
+    // the block cycle's n x kw workspaces, kw <= MG_BLOCK_COLS the widest block applied so
+    // far (leading dimension n; allocated at the first block apply, grown on demand)
+    DevBuf<double> bv, bf, bt, br;
 };
+constexpr int64_t MG_BLOCK_COLS = 32;  // widest block one block cycle takes; wider blocks run in chunks
 
 struct MultigridOp : LinOp {
     std::vector<MgLevel> levels;
@@ -605,6 +659,13 @@ struct MultigridOp : LinOp {
     Kind kind() const override { return Kind::Multigrid; }
     bool is_precond() const override { return true; }
     void apply(double *out, const double *rhs) override;
+    // The V-cycle on n x k blocks (flag FLAG_BLOCK_CYCLE; 0: apply() per column): the
+    // literal cycle of multigrid.rs:269-380 per level -- pre-smoothing, R (F - A V),
+    // mu visits, V += P V_c, post-smoothing -- through spmm_epi, with none of
+    // apply()'s single-vector folds; every column bitwise apply().  Eager launches.
+    void apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) override;
+    // launch records of one block cycle of k columns (eager, recorder on)
+    std::vector<LaunchRec> block_plan(int64_t k);
     void add_level(LinOpPtr A, LinOpPtr S, LinOpPtr R, LinOpPtr P);
     void ensure_workspace();
     void invalidate_graphs();
@@ -653,6 +714,13 @@ struct MultigridOp : LinOp {
     uint64_t flags_gen_ = 0;  // flags_generation() the graphs were captured under
     bool workspace_ready_ = false;
     bool reorder_done_ = false;
+    void ensure_block_workspace(int64_t kw);
+    void block_check(int64_t kw);  // apply()'s invariants, workspaces for kw columns, the dense tail
+    void block_run(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t kw);
+    void block_cycle(int64_t l, double *V, int64_t ldv, const double *F, int64_t ldf, int64_t kw, bool v_zero);
+    void block_smooth(int64_t l, double *&V, int64_t &ldv, double *&T, int64_t &ldt, const double *F, int64_t ldf,
+                      int64_t kw, bool v_zero);
+    DevBuf<double> perm_bf0_, perm_bv0_;  // the block cycle's perm_f0_ / perm_v0_
     DevBuf<double> perm_f0_, perm_v0_;  // the fine level's rhs / result in its numbering
     DevBuf<double> tail_M_;
     uint64_t tail_key_ = ~uint64_t(0);
@@ -664,6 +732,11 @@ void unit_vector(double *v, int64_t n, int64_t j, hipStream_t s);
 // y = x[p] / y[p] = x over n entries (reorder.hip; launch-plan records)
 void perm_gather(double *out, const double *in, const int32_t *p, int64_t n, hipStream_t s);
 void perm_scatter(double *out, const double *in, const int32_t *p, int64_t n, hipStream_t s);
+// the same over k columns (column-major blocks)
+void perm_gather_cols(double *out, int64_t ldo, const double *in, int64_t ldi, const int32_t *p, int64_t n, int64_t k,
+                      hipStream_t s);
+void perm_scatter_cols(double *out, int64_t ldo, const double *in, int64_t ldi, const int32_t *p, int64_t n, int64_t k,
+                       hipStream_t s);
 // the gather and the first Jacobi step from zero in one pass: f0 = in[p], t = d * f0
 void perm_gather_df(double *f0, double *t, const double *in, const int32_t *p, const DiagOp &D, int64_t n,
                     hipStream_t s);

@@ -617,6 +617,134 @@ static int gtc_march_occupancy(bool df, size_t dyn) {
     return n;
 }
 
+// ---- k-wide forms (spmm_gtc, the block V-cycle): kb columns per launch.  The
+// class ids, the dictionary and the value table are read once; per column the
+// window is staged and every row takes k_gtc_interp's / k_gtc_restrict's
+// dictionary walk (the marching R sums the same way), so each column is bitwise
+// the single-vector launch.  x / y advance by ldx / ldy per column.
+template <int MODE, int GP_TZ>
+__global__ __launch_bounds__(256) void k_gtc_interp_cols(GtcArgs a, int kb, int64_t ldx, int64_t ldy) {
+    constexpr int GP_WZ = GP_TZ / 2 + 2;
+    __shared__ double win[GP_WX * GP_WY * GP_WZ];
+    __shared__ uint16_t sd[G_DMAX];
+    __shared__ double st[256];
+    __shared__ int16_t lut[27];
+    const int tid = threadIdx.x;
+    const int t = a.tile0 + xcd_remap(blockIdx.x, gridDim.x);
+    const int tix = t % a.ntx, tiy = (t / a.ntx) % a.nty, tiz = t / (a.ntx * a.nty);
+    const int x0 = tix * GP_TX, y0 = tiy * GP_TY, z0 = tiz * GP_TZ;
+    const int wx0 = x0 / 2 - 1, wy0 = y0 / 2 - 1, wz0 = ((a.rz0 + z0) >> 1) - 1 - a.kz0;
+    const int64_t fplane = (int64_t)a.rx * a.ry, cplane = (int64_t)a.kx * a.ky;
+    const int lx = tid % GP_TX, ly = tid / GP_TX, gx = x0 + lx, gy = y0 + ly;
+    int cl[GP_TZ];
+    bool live[GP_TZ];
+#pragma unroll
+    for (int j = 0; j < GP_TZ; j++) {
+        const int gz = z0 + j;
+        live[j] = gx < a.rx && gy < a.ry && gz < a.rz;
+        const int64_t i = live[j] ? (int64_t)gz * fplane + (int64_t)gy * a.rx + gx : 0;
+        cl[j] = a.cls[i];
+    }
+    gtc_stage_dict<G_DMAX>(a, sd, st);
+    if (tid < 27) lut[tid] = (int16_t)(((tid / 9 - 1) * GP_WY + (tid / 3) % 3 - 1) * GP_WX + tid % 3 - 1);
+    for (int c = 0; c < kb; c++) {
+        const double *x = a.x + c * ldx;
+        double *y = a.y + c * ldy;
+        if (c) __syncthreads();  // the previous column's walk is done with win
+        for (int q = tid; q < GP_WX * GP_WY * GP_WZ; q += 256) {
+            const int X = wx0 + q % GP_WX, Y = wy0 + (q / GP_WX) % GP_WY, Z = wz0 + q / (GP_WX * GP_WY);
+            const bool in = (unsigned)X < (unsigned)a.kx && (unsigned)Y < (unsigned)a.ky && Z >= a.kz_lo && Z < a.kz_hi;
+            const int64_t zb = (int64_t)Z * cplane + (Z < 0 ? a.add_lo : Z >= a.kz ? a.add_hi : 0);
+            win[q] = in ? x[zb + (int64_t)Y * a.kx + X] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < GP_TZ; j++) {
+            if (!live[j]) continue;
+            const int gz = z0 + j;
+            const int64_t i = (int64_t)gz * fplane + (int64_t)gy * a.rx + gx;
+            double yb = 0.0;
+            if constexpr (MODE == SPMV_ADD) yb = y[i];
+            const int base = ((((a.rz0 + gz) >> 1) - a.kz0 - wz0) * GP_WY + (gy >> 1) - wy0) * GP_WX + (gx >> 1) - wx0;
+            const uint16_t *e = sd + cl[j] * a.ke;
+            double acc = 0.0;
+            for (int k = 0; k < a.ke; k += 4) {
+                double v[4], w[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const uint16_t cc = e[k + u];
+                    v[u] = st[cc >> 8];
+                    w[u] = win[base + lut[cc & 255]];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) acc = fma(v[u], w[u], acc);
+            }
+            y[i] = MODE == SPMV_SET ? acc : yb + acc;
+        }
+    }
+}
+
+template <int GR_TZ>
+__global__ __launch_bounds__(256) void k_gtc_restrict_cols(GtcArgs a, int kb, int64_t ldx, int64_t ldy) {
+    constexpr int GR_WZ = 2 * GR_TZ + 2, RL = GR_TZ / 2;
+    __shared__ double win[GR_WX * GR_WY * GR_WZ];
+    extern __shared__ uint16_t sd[];
+    __shared__ double st[256];
+    __shared__ int16_t lut[64];
+    const int tid = threadIdx.x;
+    const int t = a.tile0 + xcd_remap(blockIdx.x, gridDim.x);
+    const int tix = t % a.ntx, tiy = (t / a.ntx) % a.nty, tiz = t / (a.ntx * a.nty);
+    const int X0 = tix * GR_TX, Y0 = tiy * GR_TY, Z0 = tiz * GR_TZ;
+    const int wx0 = 2 * X0 - 1, wy0 = 2 * Y0 - 1, wz0 = 2 * (a.rz0 + Z0) - 1 - a.kz0;
+    const int64_t cplane = (int64_t)a.rx * a.ry, fplane = (int64_t)a.kx * a.ky;
+    const int lx = tid % GR_TX, ly = (tid / GR_TX) % GR_TY, lz0 = tid / (GR_TX * GR_TY);
+    bool live[RL];
+    int64_t J[RL];
+    int cls[RL];
+#pragma unroll
+    for (int j = 0; j < RL; j++) {
+        const int X = X0 + lx, Y = Y0 + ly, Z = Z0 + lz0 + 2 * j;
+        live[j] = X < a.rx && Y < a.ry && Z < a.rz;
+        J[j] = live[j] ? (int64_t)Z * cplane + (int64_t)Y * a.rx + X : 0;
+        cls[j] = a.cls[J[j]];
+    }
+    gtc_stage_dict<G_RMAX>(a, sd, st);
+    if (tid < 64) lut[tid] = (int16_t)(((tid / 16 - 1) * GR_WY + (tid / 4) % 4 - 1) * GR_WX + tid % 4 - 1);
+    constexpr int W = GR_WX * GR_WY * GR_WZ;
+    for (int c = 0; c < kb; c++) {
+        const double *x = a.x + c * ldx;
+        double *y = a.y + c * ldy;
+        if (c) __syncthreads();  // the previous column's walk is done with win
+        for (int q = tid; q < W; q += 256) {
+            const int xx = wx0 + q % GR_WX, yy = wy0 + (q / GR_WX) % GR_WY, zz = wz0 + q / (GR_WX * GR_WY);
+            const bool in = (unsigned)xx < (unsigned)a.kx && (unsigned)yy < (unsigned)a.ky && zz >= a.kz_lo && zz < a.kz_hi;
+            const int64_t zb = (int64_t)zz * fplane + (zz < 0 ? a.add_lo : zz >= a.kz ? a.add_hi : 0);
+            win[q] = in ? x[zb + (int64_t)yy * a.kx + xx] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < RL; j++) {
+            if (!live[j]) continue;
+            const int lz = lz0 + 2 * j;
+            const int base = ((2 * lz + 1) * GR_WY + 2 * ly + 1) * GR_WX + 2 * lx + 1;
+            const uint16_t *e = sd + cls[j] * a.ke;
+            double acc = 0.0;
+            for (int k = 0; k < a.ke; k += 8) {
+                double cv[8], w[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const uint16_t q = e[k + u];
+                    cv[u] = st[q >> 8];
+                    w[u] = win[base + lut[q & 255]];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) acc = fma(cv[u], w[u], acc);
+            }
+            y[J[j]] = acc;
+        }
+    }
+}
+
 // FAMG_GTC_MARCH=0: R in tiles of two coarse planes instead of marching workgroups
 static bool gtc_march_r() {
     static const bool on = env_not_zero("FAMG_GTC_MARCH");
@@ -756,6 +884,54 @@ void spmv_gtc(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
 #undef FAMG_GTCI
     }
     FAMG_CHECK_HIP(hipGetLastError());
+}
+
+// Y = R X (SET) or Y = P X / Y += P X (SET / ADD) over k columns, 8 per launch, on the
+// grid-transfer classes of a single-GPU level (no slab frame)
+void spmm_gtc(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
+              hipStream_t s) {
+    FAMG_REQUIRE(m.gtc_on && !m.rframe.on() && gtc_supports(m, mode) && mode != SPMV_ADD0 && mode != SPMV_SETDF,
+                 AMG_ERR_UNSUPPORTED, "grid-transfer SpMM: SET (R, P) or ADD (P) on a single-GPU level");
+    GtcArgs a{};
+    a.cls = m.gtc_cls.get();
+    a.dict = m.gtc_dict.get();
+    a.vtab = m.gtc_vtab.get();
+    a.ke = m.gtc_ke;
+    a.nce = m.gtc_nce;
+    a.ntab = m.gtc_ntab;
+    const int64_t *rg = m.gtc_r ? m.gtc_cg : m.gtc_fg, *kg = m.gtc_r ? m.gtc_fg : m.gtc_cg;
+    a.rx = (int)rg[0]; a.ry = (int)rg[1]; a.rz = (int)rg[2];
+    a.kx = (int)kg[0]; a.ky = (int)kg[1]; a.kz = (int)kg[2];
+    a.kz_lo = 0; a.kz_hi = a.kz; a.rz0 = 0; a.kz0 = 0; a.add_lo = a.add_hi = 0;
+    a.tile0 = 0;
+    const dim3 block(256);
+    for (int64_t c0 = 0; c0 < k; c0 += 8) {
+        const int kb = (int)std::min<int64_t>(8, k - c0);
+        a.x = x + c0 * ldx;
+        a.y = y + c0 * ldy;
+        if (m.gtc_r) {
+            a.ntx = (int)ceil_div(a.rx, GR_TX);
+            a.nty = (int)ceil_div(a.ry, GR_TY);
+            const int rtz = gtc_rtz() == 4 ? 4 : 2;
+            const dim3 grid((unsigned)((int64_t)a.ntx * a.nty * ceil_div(a.rz, rtz)));
+            const size_t dyn = (size_t)a.nce * sizeof(uint16_t);
+            if (rtz == 4) k_gtc_restrict_cols<4><<<grid, block, dyn, s>>>(a, kb, ldx, ldy);
+            else k_gtc_restrict_cols<2><<<grid, block, dyn, s>>>(a, kb, ldx, ldy);
+        } else {
+            a.ntx = (int)ceil_div(a.rx, GP_TX);
+            a.nty = (int)ceil_div(a.ry, GP_TY);
+            const int tz = gtc_tz() == 8 ? 8 : 4;
+            const dim3 grid((unsigned)((int64_t)a.ntx * a.nty * ceil_div(a.rz, tz)));
+            if (mode == SPMV_ADD) {
+                if (tz == 8) k_gtc_interp_cols<SPMV_ADD, 8><<<grid, block, 0, s>>>(a, kb, ldx, ldy);
+                else k_gtc_interp_cols<SPMV_ADD, 4><<<grid, block, 0, s>>>(a, kb, ldx, ldy);
+            } else {
+                if (tz == 8) k_gtc_interp_cols<SPMV_SET, 8><<<grid, block, 0, s>>>(a, kb, ldx, ldy);
+                else k_gtc_interp_cols<SPMV_SET, 4><<<grid, block, 0, s>>>(a, kb, ldx, ldy);
+            }
+        }
+        FAMG_CHECK_HIP(hipGetLastError());
+    }
 }
 
 }  // namespace famg

@@ -381,7 +381,7 @@ static void error_propagate(CsrOp &A, LinOp &pc, double *X, int64_t ld, int64_t 
         block_update(X, ld, AX, n, D->d.get(), n, k, out, n, s);
         return;
     }
-    for (int64_t c = 0; c < k; c++) pc.apply(T + c * n, AX + c * n);
+    pc.apply_block(T, n, AX, n, k);  // multigrid / composite: the block cycle; else column by column
     block_update(X, ld, T, n, nullptr, n, k, out, n, s);
 }
 

@@ -36,6 +36,10 @@ void LinOp::apply_in_place(double *rhs) {
     apply(rhs, inplace_scratch_.get());
 }
 
+void LinOp::apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) {
+    for (int64_t c = 0; c < k; c++) apply(out + c * ldo, rhs + c * ldr);
+}
+
 CsrPtr make_csr(Ctx *ctx) {
     auto p = std::make_shared<CsrOp>();
     p->ctx = ctx;
@@ -44,6 +48,10 @@ CsrPtr make_csr(Ctx *ctx) {
 
 void CsrOp::apply(double *out, const double *rhs) {
     spmv(m, rhs, out, SPMV_SET, SpmvEpi{}, ctx->stream);
+}
+
+void CsrOp::apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) {
+    spmm_epi(m, rhs, ldr, out, ldo, k, SPMV_SET, SpmmEpi{}, ctx->stream);
 }
 
 void CsrOp::transpose_apply(double *out, const double *rhs) {
@@ -62,6 +70,9 @@ const double *CsrOp::diagonal() {
 // ------------------------------------------------------------- diagonal
 
 void DiagOp::apply(double *out, const double *rhs) { vec_mul(out, d.get(), rhs, nrows, ctx->stream); }
+void DiagOp::apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) {
+    vec_mul_cols(out, ldo, d.get(), rhs, ldr, nrows, k, ctx->stream);
+}
 void DiagOp::apply_in_place(double *rhs) { vec_mul(rhs, d.get(), rhs, nrows, ctx->stream); }
 
 __global__ void k_jacobi_diag(const double *aii, double omega, double *d, int64_t n) {
@@ -406,6 +417,11 @@ void CoarseCholOp::apply(double *out, const double *rhs) {
     if (out == rhs) { LinOp::apply_in_place(out); return; }
     if (nb > 0) chol_env_apply(*this, out, rhs, ctx->stream);
     else dense_gemv(inv.get(), rhs, out, nrows, ctx->stream);
+}
+
+void CoarseCholOp::apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) {
+    if (nb > 0 || out == rhs) LinOp::apply_block(out, ldo, rhs, ldr, k);  // the envelope factor: per column
+    else dense_gemm_cols(inv.get(), rhs, ldr, out, ldo, nrows, k, ctx->stream);
 }
 
 // --------------------------------------------------------------- multigrid
@@ -862,6 +878,178 @@ std::vector<LaunchRec> MultigridOp::cycle_plan() {
         } else {
             cycle(0, z.get(), b.get(), true, z.get());
         }
+    }
+    FAMG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return log.recs;
+}
+
+// ------------------------------------------------------------ block V-cycle
+//
+// The cycle on n_l x kw blocks (kw <= MG_BLOCK_COLS): per level the literal steps
+// of multigrid.rs:269-380, each one k-wide launch per 8 columns where the storage
+// has an SpMM kernel.  None of cycle()'s single-vector forms (RESID0 / ADD0 folds,
+// SETDF, the marching fine launches) -- each of them is bitwise the literal form,
+// so every column of a block cycle is bitwise apply() of that column.
+
+void MultigridOp::ensure_block_workspace(int64_t kw) {
+    // (checked by size at every block apply: levels are added and the fine level's
+    // renumbering is switched on after the first one)
+    auto need = [](DevBuf<double> &b, size_t sz) {
+        if (b.size() < sz) b.resize(sz);
+    };
+    for (size_t l = 0; l < levels.size(); l++) {
+        MgLevel &L = levels[l];
+        const size_t sz = (size_t)std::max<int64_t>(1, L.A->nrows) * kw;
+        if (l > 0) { need(L.bv, sz); need(L.bf, sz); }
+        need(L.bt, sz);
+        need(L.br, sz);
+    }
+    if (levels[0].permuted) {
+        const size_t sz = (size_t)std::max<int64_t>(1, levels[0].A->nrows) * kw;
+        need(perm_bf0_, sz);
+        need(perm_bv0_, sz);
+    }
+}
+
+// smooth() on a block: Jacobi ping-pongs between (V, ldv) and (T, ldt); SGS and
+// every other smoother run per column on V (their level's A k-wide where they need it)
+void MultigridOp::block_smooth(int64_t l, double *&V, int64_t &ldv, double *&T, int64_t &ldt, const double *F,
+                               int64_t ldf, int64_t kw, bool v_zero) {
+    MgLevel &L = levels[l];
+    const int64_t n = L.A->nrows;
+    hipStream_t s = ctx->stream;
+    auto *A = dynamic_cast<CsrOp *>(L.A.get());
+    auto *D = dynamic_cast<DiagOp *>(L.S.get());
+    auto *G = dynamic_cast<SgsOp *>(L.S.get());
+    log_at(l, AMG_ROLE_SMOOTH);
+    for (int64_t it = 0; it < steps; it++) {
+        const bool zero = v_zero && it == 0;
+        if (A && D) {
+            if (zero) vec_mul_cols(T, ldt, D->d.get(), F, ldf, n, kw, s);  // 0 + d (f - A 0)
+            else spmm_epi(A->m, V, ldv, T, ldt, kw, SPMV_JACOBI, SpmmEpi{F, ldf, D->d.get()}, s);
+            std::swap(V, T);
+            std::swap(ldv, ldt);
+        } else if (A && G) {
+            if (zero) {
+                for (int64_t c = 0; c < kw; c++) G->sweep(V + c * ldv, F + c * ldf);
+            } else if (sgs_residual_form) {
+                spmm_epi(A->m, V, ldv, L.br.get(), n, kw, SPMV_RESID, SpmmEpi{F, ldf, nullptr}, s);
+                for (int64_t c = 0; c < kw; c++) G->sweep(T + c * ldt, L.br.get() + c * n);
+                vec_add_cols(V, ldv, T, ldt, n, kw, s);
+            } else {
+                for (int64_t c = 0; c < kw; c++) G->sweep_x(V + c * ldv, F + c * ldf);
+            }
+        } else {
+            if (zero) {
+                L.S->apply_block(V, ldv, F, ldf, kw);
+            } else {
+                L.A->apply_block(T, ldt, V, ldv, kw);
+                vec_sub_cols(L.br.get(), n, F, ldf, T, ldt, n, kw, s);
+                for (int64_t c = 0; c < kw; c++) L.S->apply_in_place(L.br.get() + c * n);
+                vec_add_cols(V, ldv, L.br.get(), n, n, kw, s);
+            }
+        }
+    }
+}
+
+// the result ends in (V, ldv) as passed
+void MultigridOp::block_cycle(int64_t l, double *V, int64_t ldv, const double *F, int64_t ldf, int64_t kw,
+                              bool v_zero) {
+    MgLevel &L = levels[l];
+    hipStream_t s = ctx->stream;
+    const int64_t n = L.A->nrows;
+    if (l == tail_level && v_zero) {  // the dense tail: V = M F
+        log_at(l, AMG_ROLE_COARSE);
+        dense_gemm_cols(tail_M_.get(), F, ldf, V, ldv, n, kw, s);
+        return;
+    }
+    if (l == (int64_t)levels.size() - 1) {
+        log_at(l, AMG_ROLE_COARSE);
+        L.S->apply_block(V, ldv, F, ldf, kw);
+        return;
+    }
+    double *V0 = V, *T = L.bt.get();
+    const int64_t ldv0 = ldv;
+    int64_t ldt = n;
+    auto *A = dynamic_cast<CsrOp *>(L.A.get());
+    auto *P = dynamic_cast<CsrOp *>(L.P.get());
+    MgLevel &C = levels[l + 1];
+    const int64_t nc = C.A->nrows;
+    block_smooth(l, V, ldv, T, ldt, F, ldf, kw, v_zero);
+    log_at(l, AMG_ROLE_RESID);
+    if (A) {
+        spmm_epi(A->m, V, ldv, L.br.get(), n, kw, SPMV_RESID, SpmmEpi{F, ldf, nullptr}, s);  // work = F - A V
+    } else {
+        L.A->apply_block(L.br.get(), n, V, ldv, kw);
+        vec_sub_cols(L.br.get(), n, F, ldf, L.br.get(), n, n, kw, s);
+    }
+    log_at(l, AMG_ROLE_RESTRICT);
+    L.R->apply_block(C.bf.get(), nc, L.br.get(), n, kw);  // F_c = R work
+    for (int64_t k = 0; k < mu; k++) block_cycle(l + 1, C.bv.get(), nc, C.bf.get(), nc, kw, k == 0);
+    log_at(l, AMG_ROLE_INTERP);
+    if (P) {
+        spmm_epi(P->m, C.bv.get(), nc, V, ldv, kw, SPMV_ADD, SpmmEpi{}, s);  // V += P V_c
+    } else {
+        L.P->apply_block(L.br.get(), n, C.bv.get(), nc, kw);
+        vec_add_cols(V, ldv, L.br.get(), n, n, kw, s);
+    }
+    block_smooth(l, V, ldv, T, ldt, F, ldf, kw, false);
+    log_at(l, AMG_ROLE_OTHER);
+    if (V != V0) vec_copy_cols(V0, ldv0, V, ldv, n, kw, s);
+}
+
+void MultigridOp::block_check(int64_t kw) {
+    FAMG_REQUIRE(!levels.empty(), AMG_ERR_INVALID, "empty multigrid");
+    for (size_t l = 0; l + 1 < levels.size(); l++)
+        FAMG_REQUIRE(levels[l].R && levels[l].P, AMG_ERR_INVALID, "multigrid level without R/P");
+    ensure_workspace();
+    if (flags_gen_ != flags_generation()) {
+        invalidate_graphs();
+        flags_gen_ = flags_generation();
+    }
+    ensure_tail();
+    ensure_block_workspace(kw);
+}
+
+void MultigridOp::block_run(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t kw) {
+    hipStream_t s = ctx->stream;
+    if (levels[0].permuted) {  // the fine level runs in its numbering
+        const int64_t n = levels[0].A->nrows;
+        perm_gather_cols(perm_bf0_.get(), n, rhs, ldr, levels[0].perm.get(), n, kw, s);
+        block_cycle(0, perm_bv0_.get(), n, perm_bf0_.get(), n, kw, true);
+        perm_scatter_cols(out, ldo, perm_bv0_.get(), n, levels[0].perm.get(), n, kw, s);
+    } else {
+        block_cycle(0, out, ldo, rhs, ldr, kw, true);
+    }
+}
+
+void MultigridOp::apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) {
+    if (flag(FLAG_BLOCK_CYCLE) == 0) {  // column by column: k graph-replayed cycles
+        LinOp::apply_block(out, ldo, rhs, ldr, k);
+        return;
+    }
+    std::lock_guard<std::mutex> lk(mtx);
+    FAMG_REQUIRE(out != rhs, AMG_ERR_INVALID, "multigrid apply: out must not alias rhs");
+    FAMG_REQUIRE(ldo >= nrows && ldr >= nrows, AMG_ERR_INVALID, "multigrid apply: leading dimension too small");
+    if (k <= 0) return;
+    block_check(std::min<int64_t>(k, MG_BLOCK_COLS));
+    for (int64_t c0 = 0; c0 < k; c0 += MG_BLOCK_COLS)
+        block_run(out + c0 * ldo, ldo, rhs + c0 * ldr, ldr, std::min<int64_t>(MG_BLOCK_COLS, k - c0));
+}
+
+std::vector<LaunchRec> MultigridOp::block_plan(int64_t k) {
+    std::lock_guard<std::mutex> lk(mtx);
+    FAMG_REQUIRE(k >= 1, AMG_ERR_INVALID, "block plan: need at least one column");
+    block_check(std::min<int64_t>(k, MG_BLOCK_COLS));
+    const int64_t n = levels[0].A->nrows;
+    const int64_t kw = std::min<int64_t>(k, MG_BLOCK_COLS);
+    DevBuf<double> b(std::max<int64_t>(1, n * kw)), z(std::max<int64_t>(1, n * kw));
+    vec_fill(b.get(), 1.0, n * kw, ctx->stream);
+    LaunchLog log;
+    {
+        LaunchLogScope scope(&log);
+        for (int64_t c0 = 0; c0 < k; c0 += MG_BLOCK_COLS)
+            block_run(z.get(), n, b.get(), n, std::min<int64_t>(MG_BLOCK_COLS, k - c0));
     }
     FAMG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return log.recs;

@@ -258,6 +258,44 @@ void perm_scatter(double *out, const double *in, const int32_t *p, int64_t n, hi
     log_launch("perm_scatter", -1, -1, n, 20 * n);
 }
 
+// the k-wide forms of the block cycle: column blockIdx.y of in / out (leading
+// dimensions ldi / ldo), the same permutation for every column
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void k_perm_apply_cols(double *out, int64_t ldo, const double *in, int64_t ldi,
+                                                        const int32_t *p, int64_t n) {
+    const int64_t i0 = (int64_t)blockIdx.x * (256 * PG) + threadIdx.x;
+    out += (int64_t)blockIdx.y * ldo;
+    in += (int64_t)blockIdx.y * ldi;
+    int32_t q[PG];
+    double v[PG];
+#pragma unroll
+    for (int u = 0; u < PG; u++) q[u] = p[min(i0 + 256 * u, n - 1)];
+#pragma unroll
+    for (int u = 0; u < PG; u++) v[u] = SCATTER ? in[min(i0 + 256 * u, n - 1)] : in[q[u]];
+#pragma unroll
+    for (int u = 0; u < PG; u++)
+        if (i0 + 256 * u < n) {
+            if (SCATTER) out[q[u]] = v[u];
+            else out[i0 + 256 * u] = v[u];
+        }
+}
+void perm_gather_cols(double *out, int64_t ldo, const double *in, int64_t ldi, const int32_t *p, int64_t n, int64_t k,
+                      hipStream_t s) {
+    if (n <= 0 || k <= 0) return;
+    hipLaunchKernelGGL(k_perm_apply_cols<false>, dim3((unsigned)ceil_div(n, 256 * PG), (unsigned)k), dim3(256), 0, s, out,
+                       ldo, in, ldi, p, n);
+    FAMG_CHECK_HIP(hipGetLastError());
+    log_launch("perm_gather_cols", -1, -1, n, (16 * k + 4) * n);
+}
+void perm_scatter_cols(double *out, int64_t ldo, const double *in, int64_t ldi, const int32_t *p, int64_t n, int64_t k,
+                       hipStream_t s) {
+    if (n <= 0 || k <= 0) return;
+    hipLaunchKernelGGL(k_perm_apply_cols<true>, dim3((unsigned)ceil_div(n, 256 * PG), (unsigned)k), dim3(256), 0, s, out,
+                       ldo, in, ldi, p, n);
+    FAMG_CHECK_HIP(hipGetLastError());
+    log_launch("perm_scatter_cols", -1, -1, n, (16 * k + 4) * n);
+}
+
 // How a storage sums a row: 0 one lane in stored order (3x3 blocks, SELL,
 // x-staged SELL), 1 a wave per row with a fixed lane split (wave-per-row), 2
 // depends on the row's neighbours (CSR-stream: the lanes per row follow the rows

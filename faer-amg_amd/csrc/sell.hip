@@ -782,9 +782,10 @@ __device__ __forceinline__ void spmm_walk(const char *blkp, bool paired, const i
     for (int k = 0; k < w; k += 4) spmm_step4<CM, KB>(blkp, w, k, paired, bs, lane, min(4, w - k), x, ldx, acc);
 }
 
-template <int KB>
+// MODE: the cycle's epilogue fused at the store (spmm_store; SET: the plain Y = A X)
+template <int KB, int MODE>
 __global__ __launch_bounds__(256) void spmm_sell_kernel(SellArgs a, bool paired, int64_t ldx, double *y,
-                                                        int64_t ldy) {
+                                                        int64_t ldy, SpmmEpiDev e) {
     const int blk = xcd_remap(blockIdx.x, gridDim.x);
     const int sl = __builtin_amdgcn_readfirstlane(blk * 4 + (int)(threadIdx.x >> 6));
     if (sl >= a.nslices) return;
@@ -807,7 +808,7 @@ __global__ __launch_bounds__(256) void spmm_sell_kernel(SellArgs a, bool paired,
     }
     if (live) {
 #pragma unroll
-        for (int c = 0; c < KB; c++) y[row + c * ldy] = acc[c];
+        for (int c = 0; c < KB; c++) spmm_store<MODE>(y, ldy, a.e.x, ldx, e, row, c, acc[c]);
     }
 }
 
@@ -1109,8 +1110,67 @@ void spmv_sell(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const
     FAMG_CHECK_HIP(hipGetLastError());
 }
 
-// Y = A X on fp64-valued SELL storage, SPMM_KB columns per launch
-void spmm_sell(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, hipStream_t s) {
+// Value-coded SELL over kb columns (spmm_epi): spmv_sell_kernel's decomposition --
+// the value table staged once, then each wave walks its slices once per column
+// with sell_wave, the single-vector walk (the slices come from HBM for the first
+// column and from L2 for the others, as in spmm_xs_group_kernel).  Bitwise per
+// column every single-vector kernel of the storage (generic, short, t16: the same
+// row sums in the same order).
+template <int MODE, int LAY>
+__global__ __launch_bounds__(256) void spmm_sell_coded_kernel(SellArgs a, int kb, int64_t ldx, int64_t ldy,
+                                                              int64_t ldb) {
+    constexpr int TABN = LAY == 4 ? 16 : LAY == 8 ? 256 : 1;
+    __shared__ double stab[TABN];
+    if constexpr (LAY == 4 || LAY == 8) {
+        for (int i = threadIdx.x; i < a.ntab; i += 256) stab[i] = a.vtab[i];
+        __syncthreads();
+    }
+    constexpr int SPW = sell_slices_per_wave(LAY, MODE);
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
+    const int wv = __builtin_amdgcn_readfirstlane(blk * 4 + (int)(threadIdx.x >> 6));
+    const int sl = wv * (SPW == 2 ? a.spw : 1);
+    if (sl >= a.nslices) return;
+    for (int c = 0; c < kb; c++) {
+        SellArgs b = a;
+        b.e.x += c * ldx;
+        b.e.y += c * ldy;
+        if (b.e.b) b.e.b += c * ldb;
+        sell_wave<MODE, LAY>(b, stab, sl);
+    }
+}
+
+void spmm_sell_coded(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
+                     const SpmmEpi &epi, hipStream_t s) {
+    if (m.nslices == 0) return;
+    const int lay = 4;  // (what spmv_sell passes for every coded layout)
+    const dim3 block(256);
+    for (int64_t c0 = 0; c0 < k; c0 += SPMM_KB) {
+        const int kb = (int)std::min<int64_t>(SPMM_KB, k - c0);
+        SellArgs a{m.sell_row0.get(), m.sell_soff.get(), m.sell_desc.get(), m.sell_base.get(), m.sell_data.get(), 0,
+                   (int32_t)m.nslices,
+                   Epi{x + c0 * ldx, y + c0 * ldy, epi.b ? epi.b + c0 * epi.ldb : nullptr, epi.d, nullptr, nullptr, nullptr, 0.0},
+                   m.sell_vtab.get(), (int32_t)m.sell_ntab, 1};
+        if (sell_slices_per_wave(lay, mode) == 2 && m.nslices >= SELL_PAIR_MIN_SLICES) a.spw = 2;
+        const dim3 grid((unsigned)ceil_div(m.nslices, 4 * a.spw * sell_groups_per_wave(lay)));
+#define FAMG_SELLC(LAY)                                                                                      \
+    switch (mode) {                                                                                        \
+    case SPMV_SET: spmm_sell_coded_kernel<SPMV_SET, LAY><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break;     \
+    case SPMV_ADD: spmm_sell_coded_kernel<SPMV_ADD, LAY><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break;     \
+    case SPMV_RESID: spmm_sell_coded_kernel<SPMV_RESID, LAY><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break; \
+    default: spmm_sell_coded_kernel<SPMV_JACOBI, LAY><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break;        \
+    }
+        if (m.sell_vbits == 4) { FAMG_SELLC(4) }
+        else if (m.sell_vbits == 8) { FAMG_SELLC(8) }
+        else { FAMG_SELLC(16) }
+#undef FAMG_SELLC
+        FAMG_CHECK_HIP(hipGetLastError());
+    }
+}
+
+// Y = epilogue(A X) on fp64-valued SELL storage, SPMM_KB columns per launch
+template <int MODE>
+static void spmm_sell_t(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k,
+                        const SpmmEpi &epi, hipStream_t s) {
     if (m.nslices == 0) return;
     const dim3 grid((unsigned)ceil_div(m.nslices, 4)), block(256);
     for (int64_t c0 = 0; c0 < k; c0 += SPMM_KB) {
@@ -1119,17 +1179,36 @@ void spmm_sell(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t
         SellArgs a{m.sell_row0.get(), m.sell_soff.get(), m.sell_desc.get(), m.sell_base.get(),
                    m.sell_data.get(), 0, (int32_t)m.nslices, e, nullptr, 0, 1};
         double *yc = y + c0 * ldy;
+        const SpmmEpiDev se{epi.b ? epi.b + c0 * epi.ldb : nullptr, epi.ldb, epi.d};
+#define FAMG_SELLMM(KB) \
+    hipLaunchKernelGGL((spmm_sell_kernel<KB, MODE>), grid, block, 0, s, a, m.sell_paired, ldx, yc, ldy, se)
         switch (kb) {
-        case 1: hipLaunchKernelGGL(spmm_sell_kernel<1>, grid, block, 0, s, a, m.sell_paired, ldx, yc, ldy); break;
-        case 2: hipLaunchKernelGGL(spmm_sell_kernel<2>, grid, block, 0, s, a, m.sell_paired, ldx, yc, ldy); break;
-        case 3: hipLaunchKernelGGL(spmm_sell_kernel<3>, grid, block, 0, s, a, m.sell_paired, ldx, yc, ldy); break;
-        case 4: hipLaunchKernelGGL(spmm_sell_kernel<4>, grid, block, 0, s, a, m.sell_paired, ldx, yc, ldy); break;
-        case 5: hipLaunchKernelGGL(spmm_sell_kernel<5>, grid, block, 0, s, a, m.sell_paired, ldx, yc, ldy); break;
-        case 6: hipLaunchKernelGGL(spmm_sell_kernel<6>, grid, block, 0, s, a, m.sell_paired, ldx, yc, ldy); break;
-        case 7: hipLaunchKernelGGL(spmm_sell_kernel<7>, grid, block, 0, s, a, m.sell_paired, ldx, yc, ldy); break;
-        default: hipLaunchKernelGGL(spmm_sell_kernel<8>, grid, block, 0, s, a, m.sell_paired, ldx, yc, ldy); break;
+        case 1: FAMG_SELLMM(1); break;
+        case 2: FAMG_SELLMM(2); break;
+        case 3: FAMG_SELLMM(3); break;
+        case 4: FAMG_SELLMM(4); break;
+        case 5: FAMG_SELLMM(5); break;
+        case 6: FAMG_SELLMM(6); break;
+        case 7: FAMG_SELLMM(7); break;
+        default: FAMG_SELLMM(8); break;
         }
+#undef FAMG_SELLMM
         FAMG_CHECK_HIP(hipGetLastError());
+    }
+}
+
+void spmm_sell(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, hipStream_t s) {
+    spmm_sell_t<SPMV_SET>(m, x, ldx, y, ldy, k, SpmmEpi{}, s);
+}
+
+void spmm_sell_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
+                   const SpmmEpi &epi, hipStream_t s) {
+    switch (mode) {
+    case SPMV_SET: spmm_sell_t<SPMV_SET>(m, x, ldx, y, ldy, k, epi, s); break;
+    case SPMV_ADD: spmm_sell_t<SPMV_ADD>(m, x, ldx, y, ldy, k, epi, s); break;
+    case SPMV_RESID: spmm_sell_t<SPMV_RESID>(m, x, ldx, y, ldy, k, epi, s); break;
+    case SPMV_JACOBI: spmm_sell_t<SPMV_JACOBI>(m, x, ldx, y, ldy, k, epi, s); break;
+    default: fail(AMG_ERR_INVALID, "SpMM epilogue: mode must be SET, ADD, RESID or JACOBI");
     }
 }
 

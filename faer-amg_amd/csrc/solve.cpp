@@ -1,6 +1,7 @@
 // solve.cpp -- solve loops, Composite, and their C ABI (include/amg.h).
 #include "solve.hpp"
 
+#include <algorithm>
 #include <cmath>
 
 #include "handles.hpp"
@@ -102,6 +103,44 @@ void CompositeOp::apply(double *out, const double *rhs) {
     };
     for (size_t k = comps.size(); k-- > 0;) step(*comps[k]);
     for (size_t k = 1; k < comps.size(); k++) step(*comps[k]);
+}
+
+void CompositeOp::apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) {
+    if (flag(FLAG_BLOCK_CYCLE) == 0 || k <= 0) {
+        LinOp::apply_block(out, ldo, rhs, ldr, k);
+        return;
+    }
+    std::lock_guard<std::mutex> lk(mtx);
+    FAMG_REQUIRE(out != rhs, AMG_ERR_INVALID, "composite apply: out must not alias rhs");
+    FAMG_REQUIRE(ldo >= nrows && ldr >= nrows, AMG_ERR_INVALID, "composite apply: leading dimension too small");
+    hipStream_t s = ctx->stream;
+    const int64_t n = nrows;
+    // chunks of MG_BLOCK_COLS columns, as the multigrid takes them: bounds the workspace
+    const int64_t kmax = std::min<int64_t>(k, MG_BLOCK_COLS);
+    const size_t need = (size_t)std::max<int64_t>(1, n) * kmax;
+    if (bws.size() < 2 * need) bws.resize(2 * need);
+    double *R = bws.get(), *Z = bws.get() + need;  // the residual block, a component's result
+    auto *a = dynamic_cast<CsrOp *>(A.get());
+    for (int64_t c0 = 0; c0 < k; c0 += MG_BLOCK_COLS) {
+        const int64_t kw = std::min<int64_t>(MG_BLOCK_COLS, k - c0);
+        double *o = out + c0 * ldo;
+        const double *b = rhs + c0 * ldr;
+        if (n > 0)  // OUT = +0.0
+            FAMG_CHECK_HIP(hipMemset2DAsync(o, ldo * sizeof(double), 0, n * sizeof(double), kw, s));
+        vec_copy_cols(R, n, b, ldr, n, kw, s);
+        auto step = [&](LinOp &c) {
+            c.apply_block(Z, n, R, n, kw);  // apply_in_place: copy to scratch, then apply
+            vec_add_cols(o, ldo, Z, n, n, kw, s);
+            if (a) {
+                spmm_epi(a->m, o, ldo, R, n, kw, SPMV_RESID, SpmmEpi{b, ldr, nullptr}, s);
+            } else {
+                A->apply_block(R, n, o, ldo, kw);
+                vec_sub_cols(R, n, b, ldr, R, n, n, kw, s);
+            }
+        };
+        for (size_t q = comps.size(); q-- > 0;) step(*comps[q]);
+        for (size_t q = 1; q < comps.size(); q++) step(*comps[q]);
+    }
 }
 
 }  // namespace famg

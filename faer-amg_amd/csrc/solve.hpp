@@ -42,11 +42,15 @@ int64_t pcg_impl(const SolveOps &o, const double *b, double *x, int64_t max_iter
 struct CompositeOp : LinOp {
     LinOpPtr A;
     std::vector<LinOpPtr> comps;
-    DevBuf<double> ws;
+    DevBuf<double> ws, bws;  // bws: the n x k workspace of apply_block
     std::mutex mtx;
     Kind kind() const override { return Kind::Composite; }
     bool is_precond() const override { return true; }
     void apply(double *out, const double *rhs) override;
+    // the same 2m - 1 steps on n x k blocks: each component through its apply_block,
+    // R = RHS - A OUT as one SpMM with the residual epilogue when A is a CSR matrix
+    // (flag FLAG_BLOCK_CYCLE; 0: apply() per column)
+    void apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) override;
 };
 
 // r = b - A x using the fused residual SpMV when A is a CSR matrix.

@@ -11,10 +11,14 @@
 // (ascending diagonals / offsets / block columns, fma from 0.0; the lanes-per-
 // row class kernel with the same lane split and butterfly), so every column is
 // bitwise the single-vector SpMV.  Column-major X, Y with leading dimensions.
+//
+// MODE fuses the V-cycle's epilogue at each kernel's store site (spmm_store,
+// spmv_dev.hpp: Y += A X, Y = B - A X, Y = X + d (B - A X)) for the block cycle;
+// the SET instantiations are the plain kernels.
 #include <algorithm>
 #include <type_traits>
 
-#include "famg.hpp"
+#include "spmv_dev.hpp"
 
 namespace famg {
 
@@ -33,11 +37,12 @@ struct SpmmDiaArgs {
     int64_t ldx;
     double *y;
     int64_t ldy;
+    SpmmEpiDev e;  // B, ldb, d of the fused epilogue (unread by SET)
 };
 
 // one row per lane: the row's code words once, then per column the K terms
 // fma(value, x[clamp(row + off_k)], acc) (padding terms carry +0.0 codes)
-template <int VB, int CW, int KB>
+template <int VB, int CW, int KB, int MODE>
 __global__ __launch_bounds__(256) void spmm_dia_kernel(SpmmDiaArgs a) {
     __shared__ double stab[VB == 4 ? 16 : 256];
     for (int q = threadIdx.x; q < a.ntab; q += 256) stab[q] = a.vtab[q];
@@ -58,7 +63,7 @@ __global__ __launch_bounds__(256) void spmm_dia_kernel(SpmmDiaArgs a) {
         for (int c = 0; c < KB; c++) acc[c] = fma(v, a.x[col + c * a.ldx], acc[c]);
     }
 #pragma unroll
-    for (int c = 0; c < KB; c++) a.y[row + c * a.ldy] = acc[c];
+    for (int c = 0; c < KB; c++) spmm_store<MODE>(a.y, a.ldy, a.x, a.ldx, a.e, row, c, acc[c]);
 }
 
 // ----------------------------------------------------------- stencil classes
@@ -72,6 +77,7 @@ struct SpmmScsArgs {
     int64_t ldx;
     double *y;
     int64_t ldy;
+    SpmmEpiDev e;  // B, ldb, d of the fused epilogue (unread by SET)
 };
 
 template <int IB> __device__ __forceinline__ int spmm_cls(const void *cls, int r) {
@@ -79,7 +85,7 @@ template <int IB> __device__ __forceinline__ int spmm_cls(const void *cls, int r
 }
 
 // one row per lane (spmv_scs_kernel's order: the K offsets ascending, clamped x)
-template <int IB, int KB>
+template <int IB, int KB, int MODE>
 __global__ __launch_bounds__(256) void spmm_scs_kernel(SpmmScsArgs a) {
     const int row = (int)(xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x);
     if (row >= a.nrows) return;
@@ -94,12 +100,12 @@ __global__ __launch_bounds__(256) void spmm_scs_kernel(SpmmScsArgs a) {
         for (int c = 0; c < KB; c++) acc[c] = fma(v, a.x[col + c * a.ldx], acc[c]);
     }
 #pragma unroll
-    for (int c = 0; c < KB; c++) a.y[row + c * a.ldy] = acc[c];
+    for (int c = 0; c < KB; c++) spmm_store<MODE>(a.y, a.ldy, a.x, a.ldx, a.e, row, c, acc[c]);
 }
 
 // one row per wave (spmv_scs_lanes_kernel's order: lane q takes offsets q,
 // q + 64, ... in groups of 8 steps, +0.0 past K, then the xor butterfly)
-template <int IB, int KB>
+template <int IB, int KB, int MODE>
 __global__ __launch_bounds__(256) void spmm_scs_lanes_kernel(SpmmScsArgs a) {
     const int row = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x) * 4 + (int)(threadIdx.x >> 6));
     if (row >= a.nrows) return;
@@ -135,7 +141,7 @@ __global__ __launch_bounds__(256) void spmm_scs_lanes_kernel(SpmmScsArgs a) {
     }
     if (lane == 0) {
 #pragma unroll
-        for (int c = 0; c < KB; c++) a.y[row + c * a.ldy] = acc[c];
+        for (int c = 0; c < KB; c++) spmm_store<MODE>(a.y, a.ldy, a.x, a.ldx, a.e, row, c, acc[c]);
     }
 }
 
@@ -153,11 +159,12 @@ struct SpmmBsrArgs {
     int64_t ldx;
     double *y;
     int64_t ldy;
+    SpmmEpiDev e;  // B, ldb, d of the fused epilogue (unread by SET)
 };
 
 // one node row per lane (spmv_bsr3_kernel's order: blocks ascending, dof row
 // r of block J sums v(r,0) x(3J), v(r,1) x(3J+1), v(r,2) x(3J+2) with fma)
-template <int KB>
+template <int KB, int MODE>
 __global__ __launch_bounds__(256) void spmm_bsr3_kernel(SpmmBsrArgs a) {
     const int sl = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x) * 4 + (int)(threadIdx.x >> 6));
     if (sl >= a.nslices) return;
@@ -195,7 +202,7 @@ __global__ __launch_bounds__(256) void spmm_bsr3_kernel(SpmmBsrArgs a) {
 #pragma unroll
         for (int c = 0; c < KB; c++)
 #pragma unroll
-            for (int r = 0; r < 3; r++) a.y[3 * (int64_t)I + r + c * a.ldy] = acc[c][r];
+            for (int r = 0; r < 3; r++) spmm_store<MODE>(a.y, a.ldy, a.x, a.ldx, a.e, 3 * (int64_t)I + r, c, acc[c][r]);
     }
 }
 
@@ -214,13 +221,14 @@ struct SpmmSellpArgs {
     int64_t ldx;
     double *y;
     int64_t ldy;
+    SpmmEpiDev e;  // B, ldb, d of the fused epilogue (unread by SET)
 };
 
 // spmv_sellp_kernel's sums per column: lane q of a row walks its steps t = s L + q
 // ascending with fma (fp64 values or 4/8-bit codes from the LDS table), padding
 // steps +0.0 at a clamped column, then the same xor butterfly over the L lanes.
 // A wave per slice.
-template <int L, int VB, int KB>
+template <int L, int VB, int KB, int MODE>
 __global__ __launch_bounds__(256) void spmm_sellp_kernel(SpmmSellpArgs a) {
     __shared__ double stab[VB ? 256 : 1];
     if constexpr (VB != 0) {
@@ -265,7 +273,7 @@ __global__ __launch_bounds__(256) void spmm_sellp_kernel(SpmmSellpArgs a) {
         for (int m = L / 2; m > 0; m >>= 1) acc[c] += __shfl_xor(acc[c], m);
     if (live && q == 0) {
 #pragma unroll
-        for (int c = 0; c < KB; c++) a.y[row + c * a.ldy] = acc[c];
+        for (int c = 0; c < KB; c++) spmm_store<MODE>(a.y, a.ldy, a.x, a.ldx, a.e, row, c, acc[c]);
     }
 }
 
@@ -285,23 +293,46 @@ __global__ __launch_bounds__(256) void spmm_sellp_kernel(SpmmSellpArgs a) {
 
 // Y = A X over k columns for DIA / stencil-class / 3x3-block storage; false if
 // the storage is none of these (the caller applies per column).
-bool spmm_compressed(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, hipStream_t s) {
-    const bool dia = m.kernel == SPMV_KERNEL_DIA && m.has_dia() && !m.dia_rowid && m.dia_r0 == 0 &&
-                     m.dia_r1 == m.nrows && m.dia_k <= 64;
-    const bool scs = m.kernel == SPMV_KERNEL_SCS && m.has_scs() && m.scs_seg < 0;
-    const bool bsr = m.kernel == SPMV_KERNEL_BSR && m.has_bsr();
-    const bool xs = m.kernel == SPMV_KERNEL_XS && m.has_xs();
+// MODE: the epilogue fused at the store sites (SET: none, the plain Y = A X);
+// e: its operands B (advanced with the column group here), ldb, d.
+enum SpmmKind { SPMM_NONE, SPMM_DIA, SPMM_SCS, SPMM_BSR, SPMM_SELLP, SPMM_XS };
+static SpmmKind spmm_kind(const GpuCsr &m) {
     const int sL = m.sellp_L, sV = m.sellp_vbits;
-    const bool sellp = m.kernel == SPMV_KERNEL_SELLP && m.has_sellp() && m.sellp_seg_slc.size() <= 2 &&
-                       (sL == 1 || sL == 2 || sL == 4 || sL == 8 || sL == 16 || sL == 32 || sL == 64) &&
-                       (sV == 0 || sV == 4 || sV == 8);
-    if (xs) return spmm_xs(m, x, ldx, y, ldy, k, s);  // xsell.hip: per column with its x chunks in LDS
+    if (m.kernel == SPMV_KERNEL_XS && m.has_xs()) return SPMM_XS;
+    if (m.kernel == SPMV_KERNEL_DIA && m.has_dia() && !m.dia_rowid && m.dia_r0 == 0 && m.dia_r1 == m.nrows &&
+        m.dia_k <= 64)
+        return SPMM_DIA;
+    if (m.kernel == SPMV_KERNEL_SCS && m.has_scs() && m.scs_seg < 0) return SPMM_SCS;
+    if (m.kernel == SPMV_KERNEL_BSR && m.has_bsr()) return SPMM_BSR;
+    if (m.kernel == SPMV_KERNEL_SELLP && m.has_sellp() && m.sellp_seg_slc.size() <= 2 &&
+        (sL == 1 || sL == 2 || sL == 4 || sL == 8 || sL == 16 || sL == 32 || sL == 64) &&
+        (sV == 0 || sV == 4 || sV == 8))
+        return SPMM_SELLP;
+    return SPMM_NONE;
+}
+
+bool spmm_has_kernel(const GpuCsr &m) {
+    return spmm_kind(m) != SPMM_NONE || (m.kernel == SPMV_KERNEL_SELL && !m.sell_vbits);
+}
+
+template <int MODE>
+static bool spmm_compressed_t(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k,
+                              const SpmmEpiDev &e0, hipStream_t s) {
+    const SpmmKind kind = spmm_kind(m);
+    const bool dia = kind == SPMM_DIA, scs = kind == SPMM_SCS, bsr = kind == SPMM_BSR, xs = kind == SPMM_XS;
+    const bool sellp = kind == SPMM_SELLP;
+    const int sL = m.sellp_L, sV = m.sellp_vbits;
+    if (xs) {  // xsell.hip: per column with its x chunks in LDS
+        if constexpr (MODE == SPMV_SET) return spmm_xs(m, x, ldx, y, ldy, k, s);
+        else return spmm_xs_epi(m, x, ldx, y, ldy, k, (SpmvMode)MODE, SpmmEpi{e0.b, e0.ldb, e0.d}, s);
+    }
     if (!dia && !scs && !bsr && !sellp) return false;
     if (m.nrows == 0 || k == 0) return true;
     for (int64_t c0 = 0; c0 < k; c0 += SPMM_COLS) {
         const int kb = (int)std::min<int64_t>(SPMM_COLS, k - c0);
         const double *xc = x + c0 * ldx;
         double *yc = y + c0 * ldy;
+        const SpmmEpiDev e{e0.b ? e0.b + c0 * e0.ldb : nullptr, e0.ldb, e0.d};
         if (dia) {
             SpmmDiaArgs a{};
             a.codes = m.dia_codes.get();
@@ -315,17 +346,18 @@ bool spmm_compressed(const GpuCsr &m, const double *x, int64_t ldx, double *y, i
             a.ldx = ldx;
             a.y = yc;
             a.ldy = ldy;
+            a.e = e;
             const dim3 grid((unsigned)ceil_div(m.nrows, 256)), block(256);
             const int key = m.dia_vbits * 16 + m.dia_cw;
-#define FAMG_L41(KB) spmm_dia_kernel<4, 1, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_L42(KB) spmm_dia_kernel<4, 2, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_L44(KB) spmm_dia_kernel<4, 4, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_L45(KB) spmm_dia_kernel<4, 5, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_L81(KB) spmm_dia_kernel<8, 1, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_L82(KB) spmm_dia_kernel<8, 2, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_L84(KB) spmm_dia_kernel<8, 4, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_L88(KB) spmm_dia_kernel<8, 8, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_L89(KB) spmm_dia_kernel<8, 9, KB><<<grid, block, 0, s>>>(a)
+#define FAMG_L41(KB) spmm_dia_kernel<4, 1, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_L42(KB) spmm_dia_kernel<4, 2, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_L44(KB) spmm_dia_kernel<4, 4, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_L45(KB) spmm_dia_kernel<4, 5, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_L81(KB) spmm_dia_kernel<8, 1, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_L82(KB) spmm_dia_kernel<8, 2, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_L84(KB) spmm_dia_kernel<8, 4, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_L88(KB) spmm_dia_kernel<8, 8, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_L89(KB) spmm_dia_kernel<8, 9, KB, MODE><<<grid, block, 0, s>>>(a)
             switch (key) {
             case 4 * 16 + 1: FAMG_SPMM_KB(kb, FAMG_L41) break;
             case 4 * 16 + 2: FAMG_SPMM_KB(kb, FAMG_L42) break;
@@ -340,12 +372,12 @@ bool spmm_compressed(const GpuCsr &m, const double *x, int64_t ldx, double *y, i
             }
         } else if (scs) {
             SpmmScsArgs a{m.scs_cls.get(), m.scs_dict.get(), m.scs_offs.get(), (int32_t)m.scs_k,
-                          (int32_t)m.nrows, (int32_t)m.ncols, xc, ldx, yc, ldy};
+                          (int32_t)m.nrows, (int32_t)m.ncols, xc, ldx, yc, ldy, e};
             const dim3 grid((unsigned)ceil_div(m.nrows, m.scs_lanes ? 4 : 256)), block(256);
-#define FAMG_S1(KB) spmm_scs_kernel<1, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_S2(KB) spmm_scs_kernel<2, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_SL1(KB) spmm_scs_lanes_kernel<1, KB><<<grid, block, 0, s>>>(a)
-#define FAMG_SL2(KB) spmm_scs_lanes_kernel<2, KB><<<grid, block, 0, s>>>(a)
+#define FAMG_S1(KB) spmm_scs_kernel<1, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_S2(KB) spmm_scs_kernel<2, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_SL1(KB) spmm_scs_lanes_kernel<1, KB, MODE><<<grid, block, 0, s>>>(a)
+#define FAMG_SL2(KB) spmm_scs_lanes_kernel<2, KB, MODE><<<grid, block, 0, s>>>(a)
             if (m.scs_lanes) {
                 if (m.scs_ib == 1) { FAMG_SPMM_KB(kb, FAMG_SL1) }
                 else { FAMG_SPMM_KB(kb, FAMG_SL2) }
@@ -357,9 +389,9 @@ bool spmm_compressed(const GpuCsr &m, const double *x, int64_t ldx, double *y, i
             SpmmSellpArgs a{m.sellp_vals.get(), m.sellp_eoff.get(), m.sellp_row0.get(),
                             reinterpret_cast<const int2 *>(m.sellp_pat.get()), m.sellp_offs.get(), m.sellp_rbase.get(),
                             m.sellp_vtab.get(), (int32_t)m.sellp_ntab, (int32_t)m.sellp_slices, (int32_t)m.ncols,
-                            xc, ldx, yc, ldy};
+                            xc, ldx, yc, ldy, e};
             const dim3 grid((unsigned)ceil_div(m.sellp_slices, 4)), block(256);
-#define FAMG_P(L, VB, KB) spmm_sellp_kernel<L, VB, KB><<<grid, block, 0, s>>>(a)
+#define FAMG_P(L, VB, KB) spmm_sellp_kernel<L, VB, KB, MODE><<<grid, block, 0, s>>>(a)
 #define FAMG_PL(L, VB)                                                                              \
     {                                                                                               \
         auto go = [&](auto kbc) { FAMG_P(L, VB, decltype(kbc)::value); };                           \
@@ -390,14 +422,31 @@ bool spmm_compressed(const GpuCsr &m, const double *x, int64_t ldx, double *y, i
 #undef FAMG_P
         } else {
             SpmmBsrArgs a{m.bsr_data.get(), m.bsr_row0.get(), m.bsr_soff.get(), (int32_t)m.bsr_slices,
-                          xc, ldx, yc, ldy};
+                          xc, ldx, yc, ldy, e};
             const dim3 grid((unsigned)ceil_div(m.bsr_slices, 4)), block(256);
-#define FAMG_B(KB) spmm_bsr3_kernel<KB><<<grid, block, 0, s>>>(a)
+#define FAMG_B(KB) spmm_bsr3_kernel<KB, MODE><<<grid, block, 0, s>>>(a)
             FAMG_SPMM_KB(kb, FAMG_B)
         }
         FAMG_CHECK_HIP(hipGetLastError());
     }
     return true;
+}
+
+bool spmm_compressed(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, hipStream_t s) {
+    return spmm_compressed_t<SPMV_SET>(m, x, ldx, y, ldy, k, SpmmEpiDev{nullptr, 0, nullptr}, s);
+}
+
+// the same with the cycle's epilogue fused at the store sites (spmm_epi, spmv.hip)
+bool spmm_compressed_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k,
+                         SpmvMode mode, const SpmmEpi &epi, hipStream_t s) {
+    const SpmmEpiDev e{epi.b, epi.ldb, epi.d};
+    switch (mode) {
+    case SPMV_SET: return spmm_compressed_t<SPMV_SET>(m, x, ldx, y, ldy, k, e, s);
+    case SPMV_ADD: return spmm_compressed_t<SPMV_ADD>(m, x, ldx, y, ldy, k, e, s);
+    case SPMV_RESID: return spmm_compressed_t<SPMV_RESID>(m, x, ldx, y, ldy, k, e, s);
+    case SPMV_JACOBI: return spmm_compressed_t<SPMV_JACOBI>(m, x, ldx, y, ldy, k, e, s);
+    default: fail(AMG_ERR_INVALID, "SpMM epilogue: mode must be SET, ADD, RESID or JACOBI");
+    }
 }
 
 }  // namespace famg

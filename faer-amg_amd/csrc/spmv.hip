@@ -106,6 +106,83 @@ __global__ __launch_bounds__(SPMV_BS) void spmv_stream_kernel(StreamArgs a) {
     if (rl < nrows && sub == 0) ep.store(a.e, acc);
 }
 
+// The same over kb columns (spmm_epi): the block's values and columns are staged
+// in LDS once, then every column takes spmv_stream_kernel's row sums -- the same
+// lanes per row, the same strided order, the same butterfly -- and its epilogue.
+template <int MODE>
+__global__ __launch_bounds__(SPMV_BS) void spmm_stream_kernel(StreamArgs a, int kb, int64_t ldx, int64_t ldy,
+                                                              int64_t ldb) {
+    __shared__ __attribute__((aligned(16))) double sval[SPMV_CAP + 2];
+    __shared__ __attribute__((aligned(16))) int32_t scol[SPMV_CAP + 4];
+    __shared__ double sred[SPMV_BS / 64];
+
+    const int blk = xcd_remap(blockIdx.x, a.nblocks);
+    const int r0 = a.sched[blk], r1 = a.sched[blk + 1];
+    const int e0 = a.rowptr[r0], e1 = a.rowptr[r1];
+    const int tid = threadIdx.x;
+    const int nnz = e1 - e0;
+    const Epi e0c = a.e;
+
+    if (nnz > SPMV_CAP) {  // one long row: the whole workgroup reduces it, column after column
+        for (int c = 0; c < kb; c++) {
+            Epi e = e0c;
+            e.x += c * ldx;
+            e.y += c * ldy;
+            if (e.b) e.b += c * ldb;
+            double acc = 0.0;
+            for (int k = e0 + tid; k < e1; k += SPMV_BS) acc = fma(a.val[k], gx<MODE>(e, a.col[k]), acc);
+            for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+            if (c) __syncthreads();  // the previous column's sum has been read
+            if ((tid & 63) == 0) sred[tid >> 6] = acc;
+            __syncthreads();
+            if (tid == 0) {
+                double s = sred[0];
+                for (int w = 1; w < SPMV_BS / 64; w++) s += sred[w];
+                EpiOps<MODE> ep;
+                ep.load(e, r0);
+                ep.store(e, s);
+            }
+        }
+        return;
+    }
+    const int nrows = r1 - r0;
+    int L = 1;
+    while (L < 64 && 2 * L * nrows <= SPMV_BS) L <<= 1;
+    const int rl = tid / L;
+    const int sub = tid & (L - 1);
+
+    const int bv = e0 & ~1;
+    const int nv = (e1 - bv + 1) >> 1;
+    const dbl2_t *gv = reinterpret_cast<const dbl2_t *>(a.val + bv);
+    dbl2_t *sv2 = reinterpret_cast<dbl2_t *>(sval);
+    for (int k = tid; k < nv; k += SPMV_BS) sv2[k] = __builtin_nontemporal_load(gv + k);
+    const int bc = e0 & ~3;
+    const int nc = (e1 - bc + 3) >> 2;
+    const i32x4_t *gc = reinterpret_cast<const i32x4_t *>(a.col + bc);
+    i32x4_t *sc4 = reinterpret_cast<i32x4_t *>(scol);
+    for (int k = tid; k < nc; k += SPMV_BS) sc4[k] = __builtin_nontemporal_load(gc + k);
+    __syncthreads();
+
+    const int vo = e0 - bv, co = e0 - bc;
+    int rs = 0, re = 0;
+    if (rl < nrows) {
+        rs = a.rowptr[r0 + rl] - e0;
+        re = a.rowptr[r0 + rl + 1] - e0;
+    }
+    for (int c = 0; c < kb; c++) {
+        Epi e = e0c;
+        e.x += c * ldx;
+        e.y += c * ldy;
+        if (e.b) e.b += c * ldb;
+        EpiOps<MODE> ep;
+        if (rl < nrows && sub == 0) ep.load(e, r0 + rl);
+        double acc = 0.0;
+        for (int k = rs + sub; k < re; k += L) acc = fma(sval[vo + k], gx<MODE>(e, scol[co + k]), acc);
+        for (int off = L >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        if (rl < nrows && sub == 0) ep.store(e, acc);
+    }
+}
+
 // --------------------------------------------------------------------- vector
 
 struct VecArgs {
@@ -590,6 +667,95 @@ void spmm(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy,
         return;
     }
     for (int64_t c = 0; c < k; c++) spmv(m, x + c * ldx, y + c * ldy, SPMV_SET, SpmvEpi{}, s);  // one SpMV per column
+}
+
+// Y = epilogue(A X) on CSR-stream storage, 8 columns per launch
+static void spmm_stream(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k,
+                        SpmvMode mode, const SpmmEpi &epi, hipStream_t s) {
+    if (m.nblocks <= 0) return;
+    const dim3 grid((unsigned)m.nblocks), block(256);
+    for (int64_t c0 = 0; c0 < k; c0 += 8) {
+        const int kb = (int)std::min<int64_t>(8, k - c0);
+        const Epi e{x + c0 * ldx, y + c0 * ldy, epi.b ? epi.b + c0 * epi.ldb : nullptr, epi.d, nullptr, nullptr, nullptr, 0.0};
+        StreamArgs a{m.rp32.get(), m.col.get(), m.val.get(), m.sched.get(), (int32_t)m.nblocks, e};
+        switch (mode) {
+        case SPMV_SET: spmm_stream_kernel<SPMV_SET><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break;
+        case SPMV_ADD: spmm_stream_kernel<SPMV_ADD><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break;
+        case SPMV_RESID: spmm_stream_kernel<SPMV_RESID><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break;
+        default: spmm_stream_kernel<SPMV_JACOBI><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break;
+        }
+        FAMG_CHECK_HIP(hipGetLastError());
+    }
+}
+
+// Launch-plan records of one spmm_epi() call on a storage with an SpMM kernel: one
+// per group of up to 8 columns -- the matrix bytes once, the vector traffic of
+// log_spmv per column (x read once per column, fp64 d).  gtc: the grid-transfer
+// overlay serves the call (its bytes as log_spmv counts them).
+static void log_spmm(const GpuCsr &m, SpmvMode mode, int64_t k, bool gtc = false) {
+    static const char *const names[] = {"spmm_stream", "spmm_sell", "spmm_vector", "spmm_dia", "spmm_bsr3",
+                                        "spmm_sellp",  "spmm_scs",  "spmm_xsell"};
+    const int64_t r = m.nrows;
+    const int64_t mat = gtc ? r + 2 * (int64_t)m.gtc_nce + 8 * (int64_t)m.gtc_ntab
+                        : m.kernel == SPMV_KERNEL_DIA ? 4 * (int64_t)m.dia_cw * r + 8 * m.dia_ntab : m.stream_bytes();
+    int64_t vec = 8 * m.ncols;
+    switch (mode) {
+    case SPMV_SET: vec += 8 * r; break;
+    case SPMV_ADD: vec += 16 * r; break;
+    case SPMV_RESID: vec += 16 * r; break;
+    default: vec += 24 * r; break;  // JACOBI: b, d read, y written
+    }
+    for (int64_t c0 = 0; c0 < k; c0 += 8) {
+        const int64_t kb = std::min<int64_t>(8, k - c0);
+        log_launch(gtc ? "spmm_gtc" : names[m.kernel], gtc ? SPMV_KERNEL_GTC : m.kernel, mode, r, mat + kb * vec,
+                   m.index_bytes() + kb * vec);
+    }
+}
+
+void spmm_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
+              const SpmmEpi &epi, hipStream_t s) {
+    FAMG_REQUIRE(mode >= SPMV_SET && mode <= SPMV_JACOBI, AMG_ERR_INVALID,
+                 "SpMM epilogue: mode must be SET, ADD, RESID or JACOBI");
+    FAMG_REQUIRE((mode != SPMV_RESID && mode != SPMV_JACOBI) || epi.b, AMG_ERR_INVALID, "SpMM epilogue: B required");
+    FAMG_REQUIRE(mode != SPMV_JACOBI || (epi.d && m.nrows == m.ncols), AMG_ERR_INVALID,
+                 "SpMM epilogue: JACOBI needs d and a square matrix");
+    if (k <= 0 || m.nrows == 0) return;
+    FAMG_REQUIRE(m.spmv_ready(), AMG_ERR_UNSUPPORTED, "SpMM needs nnz < 2^31 (32-bit row pointers)");
+    // The storages in spmv_route's order, so that every column is the launch the
+    // single-vector call makes: the grid-transfer overlays first (gtx per column, gtc
+    // k-wide; they sum a row in one lane, the storage below them need not), then the
+    // SpMM kernels, then value-coded SELL-64 and CSR-stream.
+    const bool gtx_first = m.gtx_on && gtx_supports(m, mode);
+    const bool gtc_first = !gtx_first && m.gtc_on && gtc_supports(m, mode);
+    if (gtc_first && !m.rframe.on()) {
+        if (g_launch_log) log_spmm(m, mode, k, true);
+        spmm_gtc(m, x, ldx, y, ldy, k, mode, s);
+        return;
+    }
+    const bool overlay = gtx_first || gtc_first;
+    if (!overlay && spmm_has_kernel(m)) {
+        if (g_launch_log) log_spmm(m, mode, k);
+        if (mode == SPMV_SET) spmm(m, x, ldx, y, ldy, k, s);
+        else if (!spmm_compressed_epi(m, x, ldx, y, ldy, k, mode, epi, s)) spmm_sell_epi(m, x, ldx, y, ldy, k, mode, epi, s);
+        return;
+    }
+    if (!overlay && m.kernel == SPMV_KERNEL_SELL && m.sell_vbits) {
+        if (g_launch_log) log_spmm(m, mode, k);
+        spmm_sell_coded(m, x, ldx, y, ldy, k, mode, epi, s);
+        return;
+    }
+    if (!overlay && m.kernel == SPMV_KERNEL_STREAM) {
+        if (g_launch_log) log_spmm(m, mode, k);
+        spmm_stream(m, x, ldx, y, ldy, k, mode, epi, s);
+        return;
+    }
+    // wave-per-row and the wide grid-transfer classes: no k-wide kernel
+    for (int64_t c = 0; c < k; c++) {
+        SpmvEpi e;
+        e.b = epi.b ? epi.b + c * epi.ldb : nullptr;
+        e.d = epi.d;
+        spmv(m, x + c * ldx, y + c * ldy, mode, e, s);
+    }
 }
 
 }  // namespace famg

@@ -33,6 +33,37 @@ struct Epi {
     double dk;          // d when it is one value (the constant-diagonal epilogues)
 };
 
+// The epilogue's arithmetic on one row sum -- the one expression every store site
+// (the single-vector kernels' EpiOps and the SpMM kernels' spmm_store) goes through.
+template <int MODE>
+__device__ __forceinline__ double epi_value(double acc, double xr, double br, double dr, double yr) {
+    if constexpr (MODE == SPMV_SET) return acc;
+    else if constexpr (MODE == SPMV_ADD || MODE == SPMV_ADD0) return yr + acc;
+    else if constexpr (MODE == SPMV_RESID || MODE == SPMV_RESID0) return br - acc;
+    else return xr + dr * (br - acc);  // JACOBI, SGS
+}
+
+// Operands of a k-wide epilogue (spmm_epi): B column-major, d shared by all columns.
+struct SpmmEpiDev {
+    const double *b;
+    int64_t ldb;
+    const double *d;
+};
+
+// The store site of an SpMM kernel: column c of row `row` (SET / ADD / RESID / JACOBI).
+template <int MODE>
+__device__ __forceinline__ void spmm_store(double *y, int64_t ldy, const double *x, int64_t ldx, const SpmmEpiDev &e,
+                                           int64_t row, int c, double acc) {
+    double xr = 0.0, br = 0.0, dr = 0.0, yr = 0.0;
+    if constexpr (MODE == SPMV_JACOBI) {
+        xr = x[row + c * ldx];
+        dr = e.d[row];
+    }
+    if constexpr (MODE == SPMV_JACOBI || MODE == SPMV_RESID) br = e.b[row + c * e.ldb];
+    if constexpr (MODE == SPMV_ADD) yr = y[row + c * ldy];
+    y[row + c * ldy] = epi_value<MODE>(acc, xr, br, dr, yr);
+}
+
 // Operands of the epilogue that do not depend on the row sum are fetched
 // before the row's loads are issued.
 template <int MODE> struct EpiOps {
@@ -51,10 +82,7 @@ template <int MODE> struct EpiOps {
         if constexpr (MODE == SPMV_ADD0) yr = (a.dc ? a.dt[a.dc[row]] : a.d[row]) * a.b[row];
     }
     __device__ __forceinline__ void store(const Epi &a, double acc) const {
-        if constexpr (MODE == SPMV_SET) a.y[i] = acc;
-        else if constexpr (MODE == SPMV_ADD || MODE == SPMV_ADD0) a.y[i] = yr + acc;
-        else if constexpr (MODE == SPMV_RESID || MODE == SPMV_RESID0) a.y[i] = br - acc;
-        else a.y[i] = xr + dr * (br - acc);  // JACOBI, SGS
+        a.y[i] = epi_value<MODE>(acc, xr, br, dr, yr);
     }
 };
 
@@ -114,12 +142,7 @@ template <int MODE, bool NT = false> struct EpiOps2 {
     }
     __device__ __forceinline__ void store(const Epi &a, double acc0, double acc1) const {
         if (!l0) return;
-        const dbl2_t acc = {acc0, acc1};
-        dbl2_t out;
-        if constexpr (MODE == SPMV_SET) out = acc;
-        else if constexpr (MODE == SPMV_ADD || MODE == SPMV_ADD0) out = yr + acc;
-        else if constexpr (MODE == SPMV_RESID || MODE == SPMV_RESID0) out = br - acc;
-        else out = xr + dr * (br - acc);  // JACOBI
+        const dbl2_t out = {epi_value<MODE>(acc0, xr.x, br.x, dr.x, yr.x), epi_value<MODE>(acc1, xr.y, br.y, dr.y, yr.y)};
         if constexpr (NT) {
             if (l1) __builtin_nontemporal_store(out, reinterpret_cast<dbl2u_t *>(a.y + i));
             else __builtin_nontemporal_store(out.x, a.y + i);

@@ -32,7 +32,7 @@
 #include <cstring>
 #include <numeric>
 
-#include "famg.hpp"
+#include "spmv_dev.hpp"
 
 namespace famg {
 
@@ -159,7 +159,10 @@ __global__ __launch_bounds__(XS_BS) void spmv_xs_kernel(XsArgs a) {
 // exactly the single-vector kernel's sums (bitwise per column), the group's
 // matrix read from HBM once and re-read from L2 / MALL for the other columns
 // (one x window fits the LDS, eight do not).
-__global__ __launch_bounds__(XS_BS) void spmm_xs_group_kernel(XsArgs a, int kb, int64_t ldx, int64_t ldy) {
+// MODE: the cycle's epilogue fused at the store (b advances with the column by ldb)
+template <int MODE>
+__global__ __launch_bounds__(XS_BS) void spmm_xs_group_kernel(XsArgs a, int kb, int64_t ldx, int64_t ldy,
+                                                              int64_t ldb) {
     __shared__ double sx[XS_MAXCH * XS_CH];
     const int g = xcd_remap(blockIdx.x, gridDim.x);
     const int c0 = a.coff[g], nch = a.coff[g + 1] - c0;
@@ -167,6 +170,7 @@ __global__ __launch_bounds__(XS_BS) void spmm_xs_group_kernel(XsArgs a, int kb, 
     const int s_end = min((g + 1) * XS_SLICES, (a.nrows + 63) / 64);
     const double *x0 = a.x;
     double *y0 = a.y;
+    const SpmmEpiDev epi{a.b, ldb, a.d};
     for (int c = 0; c < kb; c++) {
         a.x = x0 + c * ldx;
         a.y = y0 + c * ldy;
@@ -186,12 +190,14 @@ __global__ __launch_bounds__(XS_BS) void spmm_xs_group_kernel(XsArgs a, int kb, 
             const char *blk = a.data + (int64_t)(d & 0x3fffffffu) * 128;
             const double acc = (d >> 30) == 1 ? xs_walk<1, SPMV_SET>(blk, w, lane, sx, a)
                                               : xs_walk<2, SPMV_SET>(blk, w, lane, sx, a);
-            if (row < a.nrows) a.y[row] = acc;
+            if (row < a.nrows) spmm_store<MODE>(y0, ldy, x0, ldx, epi, row, c, acc);
         }
     }
 }
 
-bool spmm_xs(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, hipStream_t s) {
+template <int MODE>
+static bool spmm_xs_t(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k,
+                      const SpmmEpi &epi, hipStream_t s) {
     if (m.kernel != SPMV_KERNEL_XS || !m.has_xs()) return false;
     if (m.nrows == 0 || k == 0) return true;
     XsArgs a{};
@@ -203,14 +209,31 @@ bool spmm_xs(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t l
     a.nrows = (int32_t)m.nrows;
     a.ncols = (int32_t)m.ncols;
     a.ngroups = (int32_t)m.xs_groups;
+    a.d = epi.d;
     for (int64_t c0 = 0; c0 < k; c0 += 8) {
         a.x = x + c0 * ldx;
         a.y = y + c0 * ldy;
-        spmm_xs_group_kernel<<<dim3((unsigned)m.xs_groups), dim3(XS_BS), 0, s>>>(a, (int)std::min<int64_t>(8, k - c0),
-                                                                               ldx, ldy);
+        a.b = epi.b ? epi.b + c0 * epi.ldb : nullptr;
+        spmm_xs_group_kernel<MODE><<<dim3((unsigned)m.xs_groups), dim3(XS_BS), 0, s>>>(
+            a, (int)std::min<int64_t>(8, k - c0), ldx, ldy, epi.ldb);
         FAMG_CHECK_HIP(hipGetLastError());
     }
     return true;
+}
+
+bool spmm_xs(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, hipStream_t s) {
+    return spmm_xs_t<SPMV_SET>(m, x, ldx, y, ldy, k, SpmmEpi{}, s);
+}
+
+bool spmm_xs_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
+                 const SpmmEpi &epi, hipStream_t s) {
+    switch (mode) {
+    case SPMV_SET: return spmm_xs_t<SPMV_SET>(m, x, ldx, y, ldy, k, epi, s);
+    case SPMV_ADD: return spmm_xs_t<SPMV_ADD>(m, x, ldx, y, ldy, k, epi, s);
+    case SPMV_RESID: return spmm_xs_t<SPMV_RESID>(m, x, ldx, y, ldy, k, epi, s);
+    case SPMV_JACOBI: return spmm_xs_t<SPMV_JACOBI>(m, x, ldx, y, ldy, k, epi, s);
+    default: fail(AMG_ERR_INVALID, "SpMM epilogue: mode must be SET, ADD, RESID or JACOBI");
+    }
 }
 
 // ---------------------------------------------------------------- pipelined form

@@ -205,6 +205,10 @@ SIGNATURES = {
     "amg_smooth_vectors": (i32, [vp, vp, vp, i64, i64, i64, vp, C.c_int]),
     "amg_create_weights": (i32, [vp, vp, i64, i64, vp, C.c_int]),
     "amg_find_near_null": (i32, [vp, vp, i64, i64, i64, i64, i64, vp, C.c_int]),
+    "amg_csr_spmm_epilogue": (i32, [vp, i32, vp, i64, vp, i64, vp, i64, vp, i64]),
+    "amg_multigrid_block_plan": (i32, [vp, i64, vp, i64, P(i64)]),
+    "amg_adaptive_config_default": (i32, [vp]),
+    "amg_adaptive_build": (i32, [vp, vp, i64, i64, vp, vp, P(vp)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -503,6 +507,19 @@ class SparseMatOp(LinOp):
         with _ordered(self.ctx, AMG_MEM_DEVICE):  # y / b / d written on torch's stream
             _ck(_lib.amg_csr_spmv_epilogue(self.h, m, ptr(x), ptr(y), ptr(b), ptr(d)))
 
+    def spmm_epilogue(self, mode, X, Y, B=None, d=None):
+        """amg_csr_spmm_epilogue on column-major device blocks (n x k torch tensors
+        with stride(0) == 1): the k-wide spmv_epilogue, each column bitwise that call."""
+        m = {"set": 0, "add": 1, "resid": 2, "jacobi": 3}[mode]
+        px, _, _, k, ldx = _dptr(X)
+        py, _, _, ky, ldy = _dptr(Y)
+        if k != ky:
+            raise ValueError("X and Y must have equal columns")
+        pb, ldb = (None, 0) if B is None else (_dptr(B)[0], _dptr(B)[4])
+        with _ordered(self.ctx, AMG_MEM_DEVICE):
+            _ck(_lib.amg_csr_spmm_epilogue(self.h, m, px, ldx, py, ldy, pb, ldb,
+                                           None if d is None else vp(d.data_ptr()), k))
+
     def set_grid(self, nx, ny, nz):
         """Grid hint (amg_csr_set_grid): the rows are an nx x ny x nz grid; re-finalizes the storage."""
         _ck(_lib.amg_csr_set_grid(self.h, nx, ny, nz))
@@ -523,9 +540,15 @@ class SparseMatOp(LinOp):
         return sp.csr_matrix((va, ci, rp), shape=self.dims())
 
 
+def csr_spmm_epilogue(A, mode, X, Y, B=None, d=None):
+    """amg_csr_spmm_epilogue: the k-wide csr spmv_epilogue (SparseMatOp.spmm_epilogue, the
+    method beside SparseMatOp.spmv_epilogue, is the same call)."""
+    A.spmm_epilogue(mode, X, Y, B, d)
+
+
 FLAGS = {"fold_xscs": 0, "dia_dk": 1, "vec_wpr": 2, "gtx_time": 3, "sgs27_march": 4, "xs_pipe": 5, "bsr_kernel": 6,
          "bsr_long": 7,
-         "dia7_rp": 8, "fine_fuse": 9, "dense_tail": 10}
+         "dia7_rp": 8, "fine_fuse": 9, "dense_tail": 10, "block_cycle": 11}
 
 
 def set_flag(name, value):
@@ -732,6 +755,17 @@ class Multigrid(LinOp):
         _ck(_lib.amg_multigrid_cycle_plan(self.h, None, 0, C.byref(n)))
         recs = (LaunchRec * max(1, n.value))()
         _ck(_lib.amg_multigrid_cycle_plan(self.h, recs, n.value, C.byref(n)))
+        return [{"level": r.level, "role": ROLES.get(r.role, "?"), "kernel": r.kernel,
+                 "mode": MODES.get(r.mode, "?"), "name": r.name.decode(), "rows": r.rows,
+                 "bytes": r.bytes, "csr_bytes": r.csr_bytes} for r in recs[:n.value]]
+
+    def block_plan(self, k):
+        """The launches of one block V-cycle of k columns (amg_multigrid_block_plan),
+        as cycle_plan() lists its own."""
+        n = i64()
+        _ck(_lib.amg_multigrid_block_plan(self.h, k, None, 0, C.byref(n)))
+        recs = (LaunchRec * max(1, n.value))()
+        _ck(_lib.amg_multigrid_block_plan(self.h, k, recs, n.value, C.byref(n)))
         return [{"level": r.level, "role": ROLES.get(r.role, "?"), "kernel": r.kernel,
                  "mode": MODES.get(r.mode, "?"), "name": r.name.decode(), "rows": r.rows,
                  "bytes": r.bytes, "csr_bytes": r.csr_bytes} for r in recs[:n.value]]
@@ -994,6 +1028,50 @@ def find_near_null(A, k, iters=50, seed=0, block_size=1, strength_depth=1, X0=No
         _ck(_lib.amg_find_near_null(A.h, p, ld, k, iters, block_size, strength_depth,
                                     cfs.ctypes.data_as(vp), m))
     return X, cfs
+
+
+class AdaptiveConfig(C.Structure):
+    """amg_adaptive_config: AdaptiveConfig (adaptivity.rs) -- the SaConfig fields of
+    every hierarchy plus max_components and test_iters."""
+    _fields_ = [("sa", SaConfig), ("max_components", i64), ("test_iters", i64)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _ck(_lib.amg_adaptive_config_default(C.byref(self)))
+        sa_fields = {name for name, _ in SaConfig._fields_} - {"reserved"}
+        for k, v in kw.items():
+            if k in ("max_components", "test_iters"):
+                setattr(self, k, v)
+            elif k in sa_fields:
+                if k == "smoother" and isinstance(v, str):
+                    v = SMOOTHERS[v]
+                setattr(self.sa, k, v)
+            else:
+                raise TypeError(f"AdaptiveConfig has no option {k!r}")
+
+
+def adaptive_build(A, dim=32, seed=0, X0=None, **config):
+    """AdaptiveConfig::build (adaptivity.rs:55-165, amg_adaptive_build): near-null
+    search, a first SA hierarchy, then max_components - 1 rounds of smoothing the
+    start block with the composite built so far and building a hierarchy from what
+    survives.  The start block is default_rng(seed).standard_normal((n, dim)) or X0
+    (host, n x dim).  config: AdaptiveConfig fields (max_components, test_iters and
+    the SaConfig ones).  Returns (Composite, cfs) with cfs (max_components - 1) x dim."""
+    cfg = AdaptiveConfig(**config)
+    n = A.nrows
+    if X0 is None:
+        X = np.asfortranarray(np.random.default_rng(seed).standard_normal((n, dim)))
+    else:
+        X = _colmajor_host(X0, n)
+    if X.shape[1] != dim:
+        raise ValueError("the start block must be nrows x dim")
+    cfs = np.zeros((max(cfg.max_components - 1, 0), dim))
+    h = vp()
+    _ck(_lib.amg_adaptive_build(A.h, X.ctypes.data_as(vp), X.shape[0], dim, C.byref(cfg),
+                                cfs.ctypes.data_as(vp), C.byref(h)))
+    comp = Composite.__new__(Composite)
+    LinOp.__init__(comp, h, A.ctx, refs=(A,))
+    return comp, cfs
 
 
 def stationary_solve(A, M, b, x, max_iter=100, rel_tol=1e-8):

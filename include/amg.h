@@ -150,7 +150,12 @@ amg_status amg_set_alloc_policy(int32_t policy);
  *   flag 10 FAMG_DENSE_TAIL   the dense tail of a mu = 1 cycle: the first level
  *                             1 <= l < L - 1 of at most this many rows and every
  *                             coarser one run as one dense GEMV v = M f, M built
- *                             once from the cycle itself (default 4096; 0 = off) */
+ *                             once from the cycle itself (default 4096; 0 = off)
+ *   flag 11 FAMG_BLOCK_CYCLE  k > 1 columns through a multigrid or a Composite:
+ *                             1 (default) = one block V-cycle on the n x k block
+ *                             (k-wide kernels, the matrices read once per 8
+ *                             columns, eager launches), 0 = column by column (k
+ *                             graph-replayed cycles); the same bits either way */
 amg_status amg_set_flag(int32_t which, int64_t value);
 amg_status amg_get_flag(int32_t which, int64_t *value);
 /* Stencil-class storage of a CSR operator (structured Galerkin operators whose
@@ -183,6 +188,18 @@ amg_status amg_grid_from_offsets(const int64_t *offs, int64_t k, int64_t n, int6
  * scaled inverse diagonal).  x != y. */
 amg_status amg_csr_spmv_epilogue(const amg_linop *op, int32_t mode, const double *x, double *y,
                                  const double *b, const double *d);
+/* The k-wide counterpart (the block V-cycle's launches): column-major device
+ * blocks X (ldx), Y (ldy), B (ldb) of k columns, d one diagonal shared by all
+ * columns; modes as above; asynchronous on the context stream.  Every column is
+ * bitwise amg_csr_spmv_epilogue of that column.  Storages with an SpMM kernel
+ * (DIA codes, stencil classes, 3x3 blocks, pattern SELL, fp64 SELL-64, x-staged
+ * SELL) read the matrix once per 8 columns with the epilogue fused at the
+ * store; CSR-stream, value-coded SELL-64 and the 8-bit grid-transfer classes
+ * have k-wide launches of their single-vector row sums; wave-per-row and the
+ * wide grid-transfer classes run one SpMV per column.  X != Y; k >= 0; AMG_ERR_INVALID for a leading dimension below the
+ * rows it spans. */
+amg_status amg_csr_spmm_epilogue(const amg_linop *op, int32_t mode, const double *X, int64_t ldx, double *Y,
+                                 int64_t ldy, const double *B, int64_t ldb, const double *d, int64_t k);
 /* info12 (13 entries) = {nx, ny, nz (0: no hint), x-staged (0/1), tile tx, ty,
  * tz, halo rx, ry, rz, hint source (0 none, 1 given, 2 inferred), grid-transfer
  * classes (0 none, 1 as P, 2 as R: 8-bit gtc.hip; 3 as P, 4 as R: 16-bit
@@ -252,7 +269,10 @@ amg_status amg_linop_kind_of(const amg_linop *op, int32_t *kind);
 /* LinOp::nrows / ncols */
 amg_status amg_linop_dims(const amg_linop *op, int64_t *nrows, int64_t *ncols);
 /* LinOp::apply: out = M * rhs, out overwritten (par_spmm.rs:117,151; multigrid.rs:469).
- * out: nrows x k (ld_out), rhs: ncols x k (ld_rhs). */
+ * out: nrows x k (ld_out), rhs: ncols x k (ld_rhs).  k > 1: a CSR matrix runs one
+ * SpMM; a multigrid or a Composite runs one block cycle (flag 11; chunks of 32
+ * columns), each column bitwise the k = 1 result; AMG_MEM_HOST blocks are staged
+ * whole.  Other kinds apply column by column. */
 amg_status amg_linop_apply(amg_linop *op, double *out, int64_t ld_out, const double *rhs,
                            int64_t ld_rhs, int64_t k, amg_mem mem);
 /* BiLinOp::transpose_apply.  Supported for the symmetric operators (smoothers,
@@ -345,7 +365,8 @@ amg_status amg_multigrid_set_option(amg_linop *mg, int32_t option, int64_t value
 amg_status amg_multigrid_level_reordered(amg_linop *mg, int64_t level, int32_t *reordered);
 amg_status amg_multigrid_get_run_level(amg_linop *mg, int64_t level, amg_linop **A, amg_linop **S,
                                        amg_linop **R, amg_linop **P);
-/* Multigrid::apply == amg_linop_apply on a multigrid handle. */
+/* Multigrid::apply == amg_linop_apply on a multigrid handle (k > 1: the block
+ * V-cycle, flag 11). */
 amg_status amg_multigrid_apply(amg_linop *mg, double *out, int64_t ld_out, const double *rhs,
                                int64_t ld_rhs, int64_t k, amg_mem mem);
 
@@ -375,6 +396,13 @@ typedef struct amg_launch_rec {
     char name[32];                     /* storage kernel ("dia", "sell_short", "dia_sgs", "vec_mul" ...) */
 } amg_launch_rec;
 amg_status amg_multigrid_cycle_plan(amg_linop *mg, amg_launch_rec *recs, int64_t cap, int64_t *count);
+/* The launches of one block V-cycle of k >= 1 columns (what amg_multigrid_apply
+ * runs for k > 1 with flag 11 on), recorded the same way on scratch blocks.  A
+ * k-wide SpMM launch ("spmm_dia", "spmm_scs", "spmm_bsr3", "spmm_sellp",
+ * "spmm_sell", "spmm_xsell", "spmm_stream", "spmm_gtc") covers up to 8 columns: bytes = its matrix bytes
+ * once + its vector bytes per column; storages without an SpMM kernel show one
+ * single-vector record per column. */
+amg_status amg_multigrid_block_plan(amg_linop *mg, int64_t k, amg_launch_rec *recs, int64_t cap, int64_t *count);
 /* One of the fine level's fused launches (no reference counterpart: the fused
  * forms of multigrid.rs:341-343 and 349-369 on a constant 7-point box
  * hierarchy, fine.hip), exactly as amg_multigrid_apply makes it, on the cycle's
@@ -502,8 +530,8 @@ amg_status amg_thin_qr(amg_ctx *ctx, double *X, int64_t ld, int64_t n, int64_t k
  * cfs[c] = sqrt(ev^T A ev) / sqrt(w^T A w), ev = w - pc(A w) (:367-382; cfs host,
  * k entries, may be NULL).  A is a CSR operator (A X is one SpMM, the matrix
  * streamed once per 8 columns); pc any preconditioning handle -- a Diag
- * (Jacobi/L1/L2) runs as one fused k-wide update, every other kind is applied
- * column by column. */
+ * (Jacobi/L1/L2) runs as one fused k-wide update, a multigrid or a Composite as
+ * one block cycle (flag 11), every other kind is applied column by column. */
 amg_status amg_smooth_vectors(amg_linop *A, amg_linop *pc, double *X, int64_t ld, int64_t k, int64_t iters,
                               double *cfs, amg_mem mem);
 /* create_weights (adaptivity.rs:434-443, examples/amg/main.rs:571-580):
@@ -520,6 +548,35 @@ amg_status amg_create_weights(const amg_linop *A, const double *X, int64_t ld, i
  * convergence factors. */
 amg_status amg_find_near_null(amg_linop *A, double *X, int64_t ld, int64_t k, int64_t iters, int64_t block_size,
                               int64_t strength_depth, double *cfs, amg_mem mem);
+
+/* AdaptiveConfig::build (adaptivity.rs:55-165): from a bare SPD CSR matrix to the
+ * adaptive Composite preconditioner.  dim = coarsening_near_null_dim (32 in the
+ * reference; 2 <= dim <= 64 here, AMG_ERR_INVALID below, AMG_ERR_UNSUPPORTED
+ * above).  X0: host n x dim column-major start block (ld >= n; the ABI carries
+ * no RNG).  Steps:
+ *  1. (:56-70) amg_find_near_null on columns 1..dim-1 of a copy of X0 (dim - 1
+ *     columns, test_iters, sa.block_size, sa.strength_depth); the constant 1 in
+ *     column 0; amg_thin_qr of the n x dim block; amg_create_weights.
+ *  2. (:108-115) amg_sa_build -> the first component; Composite(A, first).
+ *  3. (:117-162) for m = 1 .. max_components - 1: amg_smooth_vectors(A,
+ *     composite, a copy of X0 (all dim columns), test_iters / (2m - 1)) -> a basis
+ *     and its convergence factors; amg_sa_build(A, basis, weights = the factors);
+ *     push the new component.  The smoothing applies the composite k-wide (the
+ *     block cycle, flag 11).
+ * cfs_out (host, may be NULL): (max_components - 1) rows of dim factors, row
+ * m - 1 from search m.  Deviations from the reference: the same start block for
+ * every search (the reference draws a new one each time); MIS aggregates in
+ * place of the modularity partitioner; target_convergence and
+ * include_constant_first_near_null have no counterpart (the reference's build
+ * reads neither).  sa.candidate_dimension must be <= dim. */
+typedef struct amg_adaptive_config {
+    amg_sa_config sa;
+    int64_t max_components; /* default 5 */
+    int64_t test_iters;     /* default 50 */
+} amg_adaptive_config;
+amg_status amg_adaptive_config_default(amg_adaptive_config *cfg);
+amg_status amg_adaptive_build(amg_linop *A, const double *X0, int64_t ld, int64_t dim,
+                              const amg_adaptive_config *cfg, double *cfs_out, amg_linop **composite_out);
 
 /* Level accessors of a multigrid: A_l, R_l, P_l (l < levels-1), smoother S_l.
  * Returned handles are new references. */
@@ -604,7 +661,8 @@ amg_status amg_comm_allreduce_sum(amg_comm *comm, double *value);
  * multicolor SGS smoother; SGS sweeps the global coloring restricted to the
  * owned rows with one halo exchange before every color (the single-GPU sweep's
  * values on every rank).  apply() maps the rank's owned rows of rhs (n_own) to
- * its owned rows of out. */
+ * its owned rows of out.  k > 1 columns run column by column: the distributed
+ * multigrid has no block cycle. */
 amg_status amg_dist_multigrid_create(amg_comm *comm, const amg_linop *mg_global,
                                      const int64_t *level_splits, int64_t agglomerate_rows,
                                      amg_linop **out);

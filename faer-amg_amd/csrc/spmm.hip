@@ -103,8 +103,11 @@ __global__ __launch_bounds__(256) void spmm_scs_kernel(SpmmScsArgs a) {
     for (int c = 0; c < KB; c++) spmm_store<MODE>(a.y, a.ldy, a.x, a.ldx, a.e, row, c, acc[c]);
 }
 
-// one row per wave (spmv_scs_lanes_kernel's order: lane q takes offsets q,
-// q + 64, ... in groups of 8 steps, +0.0 past K, then the xor butterfly)
+// one row per wave (spmv_scs_lanes_kernel's order: lane q takes the offset pairs
+// 2q, 2q + 1 of every 128-offset block, blocks ascending, the pair's first term
+// before its second; past K -- a multiple of 8, so a pair is inside or outside as
+// one -- +0.0 at the row itself; then the xor butterfly): every column is bitwise
+// the single-vector launch
 template <int IB, int KB, int MODE>
 __global__ __launch_bounds__(256) void spmm_scs_lanes_kernel(SpmmScsArgs a) {
     const int row = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x) * 4 + (int)(threadIdx.x >> 6));
@@ -114,25 +117,26 @@ __global__ __launch_bounds__(256) void spmm_scs_lanes_kernel(SpmmScsArgs a) {
     double acc[KB];
 #pragma unroll
     for (int c = 0; c < KB; c++) acc[c] = 0.0;
-    int k0 = 0;
-    for (; k0 + 8 * 64 <= a.k; k0 += 8 * 64) {
+    const int nb = (a.k + 127) >> 7;
+#pragma unroll 2
+    for (int j = 0; j < nb; j++) {
+        const int kk = 128 * j + 2 * lane;
+        const bool in = kk < a.k;
+        const int2 of = in ? *reinterpret_cast<const int2 *>(a.offs + kk) : int2{0, 0};
+        const spmm_dbl2_t v = in ? *reinterpret_cast<const spmm_dbl2_t *>(dct + kk) : spmm_dbl2_t{0.0, 0.0};
+        const int64_t c0 = min(max(row + of.x, 0), a.ncols - 1);
+        const int64_t c1 = min(max(row + of.y, 0), a.ncols - 1);
+        double x0[KB], x1[KB];
 #pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int k = k0 + 64 * u + lane;
-            const double v = dct[k];
-            const int64_t col = min(max(row + a.offs[k], 0), a.ncols - 1);
-#pragma unroll
-            for (int c = 0; c < KB; c++) acc[c] = fma(v, a.x[col + c * a.ldx], acc[c]);
+        for (int c = 0; c < KB; c++) {
+            x0[c] = a.x[c0 + c * a.ldx];
+            x1[c] = a.x[c1 + c * a.ldx];
         }
-    }
 #pragma unroll
-    for (int u = 0; u < 8; u++) {
-        const int k = k0 + 64 * u + lane;
-        const int kc = min(k, a.k - 1);
-        const double v = k < a.k ? dct[kc] : 0.0;
-        const int64_t col = min(max(row + a.offs[kc], 0), a.ncols - 1);
-#pragma unroll
-        for (int c = 0; c < KB; c++) acc[c] = fma(v, a.x[col + c * a.ldx], acc[c]);
+        for (int c = 0; c < KB; c++) {
+            acc[c] = fma(v.x, x0[c], acc[c]);
+            acc[c] = fma(v.y, x1[c], acc[c]);
+        }
     }
 #pragma unroll
     for (int c = 0; c < KB; c++) {

@@ -121,7 +121,8 @@ def test_spmm_epilogue_classes_and_pattern_sell(ctx):
     classes and pattern SELL, on the smallest operators that have them.  Its class
     levels all run one row per lane (measured: levels 1 and 2; the one-row-per-wave
     kernel needs an operator of >= 256 offsets without a grid, which no hierarchy
-    built here has), so spmm_scs_lanes_kernel's epilogues are not reached."""
+    built here has): spmm_scs_lanes_kernel and its epilogues are checked on banded
+    operators in tests/test_gpu_row_per_wave.py."""
     F = fa()
     dims = (128, 128, 128)
     A = F.SparseMatOp.laplace3d_7pt(ctx, *dims)

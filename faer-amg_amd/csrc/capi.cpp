@@ -409,6 +409,13 @@ amg_status amg_csr_grid_info(const amg_linop *op, int64_t *info12) {
     });
 }
 
+amg_status amg_csr_row_lanes(const amg_linop *op, int64_t *lanes) {
+    return guard([&] {
+        FAMG_REQUIRE(lanes, AMG_ERR_INVALID, "null argument");
+        *lanes = xscs_row_lanes(need_csr(op)->m);
+    });
+}
+
 amg_status amg_csr_dia_range(const amg_linop *op, int64_t *info4) {
     return guard([&] {
         FAMG_REQUIRE(info4, AMG_ERR_INVALID, "null argument");

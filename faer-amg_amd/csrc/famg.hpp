@@ -174,6 +174,7 @@ struct GpuCsr {
     int xscs_ws = 0;  // LDS row stride of the window (>= wx; padded against bank conflicts)
     int xscs_tile_src = 0;  // how the tile was chosen: TuneSource (tuning.hpp)
     bool xscs_fdiv = false;  // the tile's float-reciprocal divisions checked exact (xscs_set_tile)
+    bool xscs_split = false;  // few long rows: eight lanes per row (spmv_xscs_split_kernel)
     DevBuf<int32_t> xscs_lo;
     std::vector<int> xscs_steps;  // (dx, dy, dz) of each of the scs_k offsets
     // grid-transfer classes (gtc.hip) for R/P of a 2x2x2-box hierarchy: an overlay
@@ -407,6 +408,9 @@ inline bool epi_dconst(const SpmvEpi &epi) { return epi.dc && epi.dk != 0.0 && f
 void dia_route(const GpuCsr &m, const SpmvEpi &epi, SpmvRoute &r);
 bool sell_takes_short(const GpuCsr &m, SpmvMode mode, int64_t seg);
 bool scs_takes_xscs(const GpuCsr &m, int64_t seg);
+// lanes that share a row sum of the x-staged class kernel: 8 on few long rows
+// (spmv_xscs_split_kernel), else 1 -- also for storages without that kernel
+int xscs_row_lanes(const GpuCsr &m);
 void spmv_dia(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
               const SpmvRoute &r);
 void spmv_dia_sgs(const GpuCsr &m, const double *x, double *y, const SpmvEpi &epi, hipStream_t s,

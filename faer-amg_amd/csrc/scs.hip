@@ -29,6 +29,7 @@
 #include <unordered_map>
 
 #include "famg.hpp"
+#include "spmv_dev.hpp"
 #include "tuning.hpp"
 
 namespace famg {
@@ -227,6 +228,39 @@ struct XscsArgs {
     float rwx, rwy, rtx, rty;
 };
 
+// Stage the x window of the tile at (x0, y0, z0) with the workgroup's nt threads:
+// rows of wx consecutive x values, 0.0 outside the grid.  RESID0 (the zero-guess
+// step folded into the residual): the staged operand is the iterate d*x that
+// vec_mul(_coded) would have stored, so the sums are the unfolded residual's
+// bitwise.  The caller synchronizes.
+template <int MODE>
+__device__ __forceinline__ void xscs_stage(const XscsArgs &a, double *win, int tid, int nt, int x0, int y0, int z0,
+                                           int64_t plane) {
+    const int W = a.wx * a.wy * a.wz;
+    constexpr int PF = 8;
+    for (int p0 = tid; p0 < W; p0 += nt * PF) {
+        double v[PF];
+        int si[PF];
+#pragma unroll
+        for (int u = 0; u < PF; u++) {
+            const int p = p0 + nt * u;
+            const int q = fdiv_rcp(p, a.rwx), pz = fdiv_rcp(q, a.rwy);
+            const int px = p - q * a.wx, py = q - pz * a.wy;
+            si[u] = q * a.ws + px;  // (pz wy + py) ws + px
+            const int gx = x0 - a.rx + px, gy = y0 - a.ry + py, gz = z0 - a.rz + pz;
+            const bool in = p < W && (unsigned)gx < (unsigned)a.nx && (unsigned)gy < (unsigned)a.ny && gz >= a.zlo &&
+                            gz < a.zhi;
+            const int64_t g = (int64_t)gz * plane + (gz < 0 ? a.add_lo : gz >= a.nz ? a.add_hi : 0) +
+                              (int64_t)gy * a.nx + gx;
+            if constexpr (MODE == SPMV_RESID0) v[u] = in ? (a.dc ? a.dt[a.dc[g]] : a.d[g]) * a.x[g] : 0.0;
+            else v[u] = in ? a.x[g] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < PF; u++)
+            if (p0 + nt * u < W) win[si[u]] = v[u];
+    }
+}
+
 // Two rows per lane under 8-bit class ids (A_1 of the 256^3 cycle: 4096 workgroups, 16 per
 // CU, windows of ~14 KB) are bounded to 96 VGPRs, five waves per SIMD: the JACOBI epilogue
 // took 128 (four; C2 A_1 JACOBI 33.1 -> 31.1 us, no scratch; the other epilogues already fit).
@@ -271,33 +305,7 @@ __global__ __launch_bounds__(256, (RL == 2 && IB == 1) ? 5 : 1) void spmv_xscs_k
             }
         }
     }
-    // stage the window: rows of wx consecutive x values, 0.0 outside the grid.
-    // RESID0 (the zero-guess step folded into the residual): the staged operand
-    // is the iterate d*x that vec_mul(_coded) would have stored, so the sums are
-    // the unfolded residual's bitwise
-    const int W = a.wx * a.wy * a.wz;
-    constexpr int PF = 8;
-    for (int p0 = tid; p0 < W; p0 += 256 * PF) {
-        double v[PF];
-        int si[PF];
-#pragma unroll
-        for (int u = 0; u < PF; u++) {
-            const int p = p0 + 256 * u;
-            const int q = fdiv_rcp(p, a.rwx), pz = fdiv_rcp(q, a.rwy);
-            const int px = p - q * a.wx, py = q - pz * a.wy;
-            si[u] = q * a.ws + px;  // (pz wy + py) ws + px
-            const int gx = x0 - a.rx + px, gy = y0 - a.ry + py, gz = z0 - a.rz + pz;
-            const bool in = p < W && (unsigned)gx < (unsigned)a.nx && (unsigned)gy < (unsigned)a.ny && gz >= a.zlo &&
-                            gz < a.zhi;
-            const int64_t g = (int64_t)gz * plane + (gz < 0 ? a.add_lo : gz >= a.nz ? a.add_hi : 0) +
-                              (int64_t)gy * a.nx + gx;
-            if constexpr (MODE == SPMV_RESID0) v[u] = in ? (a.dc ? a.dt[a.dc[g]] : a.d[g]) * a.x[g] : 0.0;
-            else v[u] = in ? a.x[g] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < PF; u++)
-            if (p0 + 256 * u < W) win[si[u]] = v[u];
-    }
+    xscs_stage<MODE>(a, win, tid, 256, x0, y0, z0, plane);
     __syncthreads();
     if constexpr (MODE == SPMV_JACOBI) {
 #pragma unroll
@@ -378,6 +386,93 @@ __global__ __launch_bounds__(256, (RL == 2 && IB == 1) ? 5 : 1) void spmv_xscs_k
     }
 }
 
+// Few long rows on an x-staged level (A_3 of the 256^3 cycle: 32768 rows of 787
+// offsets, nearly every row its own class): one lane per row leaves 512 waves on
+// 1024 SIMDs, each a chain of k / 8 dependent dictionary round trips, and every
+// lane of a wave reads another dictionary row.  Here eight adjacent lanes share a
+// row: lane j takes the offset pairs (2 (j + 8 s), 2 (j + 8 s) + 1), s = 0, 1, ...
+// -- the group's eight 16-B dictionary loads of a step are one 128-B line -- with
+// x from the staged window at lo[], which is staged in LDS behind the window.  A
+// tile of more than XSPLIT_ROWS rows is walked in passes over the same window.
+// Row sum: the lane's fma chain in ascending s, then the eight partial sums through
+// __shfl_xor with masks 1, 2, 4 -- an order fixed by k alone, so a row has the same
+// bits under any tile, pass, frame or rank; it is not the oracle's sequential
+// order (rounding-level differences, as the dense tail and the row-per-wave kernels).
+// 16-bit class ids only: an operator of >= 256 offsets on a grid has more than 256
+// truncation classes, so 8-bit ids stay on spmv_xscs_kernel.
+constexpr int XSPLIT_LANES = 8;
+constexpr int XSPLIT_ROWS = 128;  // rows per pass: 1024 threads
+constexpr int XSPLIT_US = 4;      // steps whose loads are issued before the first wait
+template <int MODE>
+__global__ __launch_bounds__(XSPLIT_LANES * XSPLIT_ROWS) void spmv_xscs_split_kernel(XscsArgs a) {
+    extern __shared__ double win[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int t = a.tile0 + xcd_remap(blockIdx.x, gridDim.x);
+    const int tix = t % a.ntx, tiy = (t / a.ntx) % a.nty, tiz = t / (a.ntx * a.nty);
+    const int x0 = tix * a.tx, y0 = tiy * a.ty, z0 = tiz * a.tz;
+    const int T = a.tx * a.ty * a.tz;
+    const int64_t plane = (int64_t)a.nx * a.ny;
+    int *llo = reinterpret_cast<int *>(win + a.ws * a.wy * a.wz);
+    xscs_stage<MODE>(a, win, tid, nt, x0, y0, z0, plane);
+    for (int q = tid; q < a.k; q += nt) llo[q] = a.lo[q];
+    __syncthreads();
+    const int g = tid >> 3, j = tid & (XSPLIT_LANES - 1);
+    const int full = a.k >> 4;                   // steps that cover all eight lanes
+    const bool half = (a.k & 8) != 0 && j < 4;   // k = 16 m + 8: the last step covers lanes 0-3
+    const int *lj = llo + 2 * j;
+    for (int r0 = 0; r0 < T; r0 += XSPLIT_ROWS) {
+        const int lt = r0 + g;
+        const int lq = fdiv_rcp(lt, a.rtx), lz = fdiv_rcp(lq, a.rty);
+        const int lx = lt - lq * a.tx, ly = lq - lz * a.ty;
+        const int gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
+        const bool live = lt < T && gx < a.nx && gy < a.ny && gz < a.nz;
+        const int64_t gi = live ? (int64_t)gz * plane + (int64_t)gy * a.nx + gx
+                                : (int64_t)z0 * plane + (int64_t)y0 * a.nx + x0;  // the tile's first point
+        const int wb = live ? ((lz + a.rz) * a.wy + ly + a.ry) * a.ws + lx + a.rx : (a.rz * a.wy + a.ry) * a.ws + a.rx;
+        const int c = static_cast<const uint16_t *>(a.cls)[gi];
+        double br = 0.0, xr = 0.0, dr = 0.0, yr = 0.0;
+        const bool head = live && j == 0;  // the lane of the epilogue
+        if (head) {
+            if constexpr (MODE == SPMV_RESID || MODE == SPMV_RESID0) br = a.b[gi];
+            if constexpr (MODE == SPMV_ADD) yr = a.y[gi];
+            if constexpr (MODE == SPMV_JACOBI) {
+                br = a.b[gi];
+                dr = a.dc ? a.dt[a.dc[gi]] : a.d[gi];
+                xr = win[wb];  // the staged x_i (the window holds x itself)
+            }
+        }
+        const double *dj = a.dict + (int64_t)c * a.k + 2 * j;
+        double acc = 0.0;
+        auto steps = [&](auto us, int s) {
+            constexpr int US = decltype(us)::value;
+            scs_dbl2a_t v[US];
+            int2 l[US];
+            double xa[US], xb[US];
+#pragma unroll
+            for (int u = 0; u < US; u++) v[u] = *reinterpret_cast<const scs_dbl2a_t *>(dj + 16 * (s + u));
+#pragma unroll
+            for (int u = 0; u < US; u++) l[u] = *reinterpret_cast<const int2 *>(lj + 16 * (s + u));
+#pragma unroll
+            for (int u = 0; u < US; u++) {
+                xa[u] = win[wb + l[u].x];
+                xb[u] = win[wb + l[u].y];
+            }
+#pragma unroll
+            for (int u = 0; u < US; u++) {
+                acc = fma(v[u].x, xa[u], acc);
+                acc = fma(v[u].y, xb[u], acc);
+            }
+        };
+        int s = 0;
+        for (; s + XSPLIT_US <= full; s += XSPLIT_US) steps(std::integral_constant<int, XSPLIT_US>{}, s);
+        for (; s < full; s++) steps(std::integral_constant<int, 1>{}, s);
+        if (half) steps(std::integral_constant<int, 1>{}, full);
+#pragma unroll
+        for (int m = 1; m < XSPLIT_LANES; m <<= 1) acc += __shfl_xor(acc, m);
+        if (head) a.y[gi] = epi_value<MODE>(acc, xr, br, dr, yr);
+    }
+}
+
 // the lanes-per-row kernel for row ranges of < SCS_LANES_ROWS rows with >= 256
 // offsets (A/B switch FAMG_SCS_LANES=0: no stencil classes for them)
 constexpr int64_t SCS_LANES_ROWS = 131072;
@@ -406,6 +501,7 @@ void scs_release(GpuCsr &m) {
     m.scs_lanes = false;
     m.xscs = false;
     m.xscs_tile_src = 0;
+    m.xscs_split = false;
     m.xscs_lo.release();
 }
 
@@ -415,6 +511,25 @@ static bool xscs_enabled() {
     static const bool on = env_not_zero("FAMG_XSCS");
     return on;
 }
+
+// A/B switch FAMG_XSCS_SPLIT=0: x-staged levels of few long rows keep one lane per
+// row (spmv_xscs_kernel); read at every storage build, like FAMG_XSCS_TILE
+static bool xscs_split_enabled() { return env_not_zero("FAMG_XSCS_SPLIT"); }
+
+// LDS the eight-lanes-per-row kernel keeps behind the window: its k window offsets
+// (tiles and window strides are chosen to leave that room within 64 KB)
+static int64_t xscs_lo_bytes(const GpuCsr &m, int k) { return m.xscs_split ? (int64_t)k * 4 : 0; }
+
+// LDS of the x-staged kernels for m's tile
+static size_t xscs_lds(const GpuCsr &m) {
+    const size_t win = (size_t)m.xscs_ws * (m.xscs_t[1] + 2 * m.xscs_r[1]) * (m.xscs_t[2] + 2 * m.xscs_r[2]) * sizeof(double);
+    return win + (size_t)xscs_lo_bytes(m, (int)m.scs_k);
+}
+
+// the eight-lanes-per-row kernel takes m's launches
+static bool xscs_takes_split(const GpuCsr &m) { return m.xscs && m.xscs_split; }
+
+int xscs_row_lanes(const GpuCsr &m) { return m.has_scs() && xscs_takes_split(m) ? XSPLIT_LANES : 1; }
 
 // The grid hint applies to the whole square matrix.
 static bool grid_applies(const GpuCsr &m) {
@@ -431,9 +546,9 @@ static bool grid_applies(const GpuCsr &m) {
 // so the row positions decide.  A_1 of the 7-point cycle on 8 x 8 x 8 tiles:
 // stride 12 put rows y and y + 3 on the same banks (PMC: 45 % of the LDS cycles
 // were bank conflicts).
-static int xscs_stride(const int *t, int wx, int wy, int wz) {
+static int xscs_stride(const int *t, int wx, int wy, int wz, int64_t rsv) {
     int best = wx, best_cost = 1 << 30;
-    for (int s = wx; s < wx + 32 && (int64_t)s * wy * wz * 8 <= 64 * 1024; s++) {
+    for (int s = wx; s < wx + 32 && (int64_t)s * wy * wz * 8 + rsv <= 64 * 1024; s++) {
         int cost = 0;
         for (int g = 0; g < 2; g++) {
             int cnt[64] = {0};
@@ -456,8 +571,8 @@ static int xscs_stride(const int *t, int wx, int wy, int wz) {
 static void xscs_set_tile(GpuCsr &m, const int *t) {
     const int rx = m.xscs_r[0], ry = m.xscs_r[1], rz = m.xscs_r[2];
     const int wx = t[0] + 2 * rx, wy = t[1] + 2 * ry;
-    const int ws = xscs_stride(t, wx, wy, t[2] + 2 * rz);
     const int Kp = (int)(m.xscs_steps.size() / 3);
+    const int ws = xscs_stride(t, wx, wy, t[2] + 2 * rz, xscs_lo_bytes(m, Kp));
     std::vector<int32_t> lo(Kp);
     for (int k = 0; k < Kp; k++)
         lo[k] = (m.xscs_steps[3 * k + 2] * wy + m.xscs_steps[3 * k + 1]) * ws + m.xscs_steps[3 * k];
@@ -530,7 +645,7 @@ static bool xscs_setup(GpuCsr &m, const std::vector<int32_t> &offs, int Kp, cons
             for (int tz : cands(nz, true)) {
                 const int64_t T = (int64_t)tx * ty * tz;
                 const int64_t W = (int64_t)(tx + 2 * rx) * (ty + 2 * ry) * (tz + 2 * rz);
-                if (T > 1024 || T < std::min<int64_t>(64, n) || W * 8 > 64 * 1024) continue;
+                if (T > 1024 || T < std::min<int64_t>(64, n) || W * 8 + xscs_lo_bytes(m, Kp) > 64 * 1024) continue;
                 // one row per lane wherever the grid gives >= 1024 such tiles: the
                 // walk is latency-bound, so resident waves matter more than halo
                 // bytes (A_2 of the 256^3 cycle: 1024-row tiles, one wave per SIMD,
@@ -549,7 +664,7 @@ static bool xscs_setup(GpuCsr &m, const std::vector<int32_t> &offs, int Kp, cons
     if (const char *e = getenv("FAMG_XSCS_TILE")) {
         int t0, t1, t2;
         if (sscanf(e, "%d,%d,%d", &t0, &t1, &t2) == 3 && t0 > 0 && t1 > 0 && t2 > 0 && t0 * t1 * t2 <= 1024 &&
-            (int64_t)(t0 + 2 * rx) * (t1 + 2 * ry) * (t2 + 2 * rz) * 8 <= 64 * 1024) {
+            (int64_t)(t0 + 2 * rx) * (t1 + 2 * ry) * (t2 + 2 * rz) * 8 + xscs_lo_bytes(m, Kp) <= 64 * 1024) {
             best[0] = t0; best[1] = t1; best[2] = t2;
         }
     }
@@ -647,7 +762,7 @@ static void xscs_autotune(GpuCsr &m) {
                 if (tx > nx || ty > ny || tz > nz) continue;
                 const int64_t T = (int64_t)tx * ty * tz;
                 const int64_t W = (int64_t)(tx + 2 * rx) * (ty + 2 * ry) * (tz + 2 * rz);
-                if (T < std::min<int64_t>(64, n) || T > 1024 || W * 8 > 64 * 1024) continue;
+                if (T < std::min<int64_t>(64, n) || T > 1024 || W * 8 + xscs_lo_bytes(m, (int)m.scs_k) > 64 * 1024) continue;
                 if (T < 128 && n >= 1024 * 256) continue;
                 if (tx < 8 && nx >= 8) continue;  // short x rows stage poorly (ab_xscs)
                 cands.push_back({tx, ty, tz});
@@ -781,8 +896,12 @@ bool build_scs(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes) {
     // FAMG_SCS_ROWS=1: few long rows take the lanes-per-row kernel even where the
     // x-staged one applies (A/B)
     const bool rows_pref = scs_rows_pref() && r1 - r0 < SCS_LANES_ROWS && Kp >= 256 && !framed;
+    // few long rows, the rule of the wave-per-row class kernel: x-staged with eight
+    // lanes per row (set first: the tile must leave LDS for the window offsets)
+    m.xscs_split = ib == 2 && r1 - r0 < SCS_LANES_ROWS && Kp >= 256 && xscs_split_enabled();
     const bool xs3 = !rows_pref && on_grid && dict_bytes <= (int64_t(256) << 20) &&
                      (framed || (double)stream <= 0.5 * (double)other_bytes) && xscs_setup(m, offs, Kp, rp, col, val);
+    m.xscs_split = m.xscs_split && xs3;
     if (!xs3 && (K < SCS_KMIN || small_table || framed)) return false;
     // few long rows: one row per wave, the dictionary streamed (up to 256 MiB)
     const bool lanes = !xs3 && r1 - r0 < SCS_LANES_ROWS && Kp >= 256;
@@ -870,8 +989,23 @@ static void spmv_xscs(const GpuCsr &m, const double *x, double *y, SpmvMode mode
     a.x = x; a.y = y; a.b = epi.b; a.d = epi.d; a.dc = epi.dc; a.dt = epi.dt;
     const int T = a.tx * a.ty * a.tz;
     const int rl = T <= 256 ? 1 : T <= 512 ? 2 : 4;
-    const size_t lds = (size_t)a.ws * a.wy * a.wz * sizeof(double);
+    const bool split = xscs_takes_split(m);
+    const size_t lds = xscs_lds(m);
+    FAMG_REQUIRE(lds <= 64 * 1024, AMG_ERR_UNSUPPORTED, "x-staged classes: window beyond 64 KB");
     const dim3 grid((unsigned)((int64_t)a.ntx * a.nty * (tz1 - tz0))), block(256);
+    if (split) {  // eight lanes per row, whole waves
+        const dim3 blk((unsigned)(ceil_div(XSPLIT_LANES * std::min(T, XSPLIT_ROWS), 64) * 64));
+        switch (mode) {
+        case SPMV_SET: spmv_xscs_split_kernel<SPMV_SET><<<grid, blk, lds, s>>>(a); break;
+        case SPMV_ADD: spmv_xscs_split_kernel<SPMV_ADD><<<grid, blk, lds, s>>>(a); break;
+        case SPMV_RESID: spmv_xscs_split_kernel<SPMV_RESID><<<grid, blk, lds, s>>>(a); break;
+        case SPMV_RESID0: spmv_xscs_split_kernel<SPMV_RESID0><<<grid, blk, lds, s>>>(a); break;
+        case SPMV_JACOBI: spmv_xscs_split_kernel<SPMV_JACOBI><<<grid, blk, lds, s>>>(a); break;
+        default: fail(AMG_ERR_UNSUPPORTED, "stencil-class storage: unsupported SpMV epilogue");
+        }
+        FAMG_CHECK_HIP(hipGetLastError());
+        return;
+    }
 #define FAMG_XS3(M, IB)                                                                            \
     if (rl == 1) spmv_xscs_kernel<M, IB, 1><<<grid, block, lds, s>>>(a);                           \
     else if (rl == 2) spmv_xscs_kernel<M, IB, 2><<<grid, block, lds, s>>>(a);                      \

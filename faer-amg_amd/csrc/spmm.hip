@@ -306,7 +306,8 @@ static SpmmKind spmm_kind(const GpuCsr &m) {
     if (m.kernel == SPMV_KERNEL_DIA && m.has_dia() && !m.dia_rowid && m.dia_r0 == 0 && m.dia_r1 == m.nrows &&
         m.dia_k <= 64)
         return SPMM_DIA;
-    if (m.kernel == SPMV_KERNEL_SCS && m.has_scs() && m.scs_seg < 0) return SPMM_SCS;
+    // (eight lanes per row: no k-wide kernel sums in that order, spmm_epi runs one SpMV per column)
+    if (m.kernel == SPMV_KERNEL_SCS && m.has_scs() && m.scs_seg < 0 && xscs_row_lanes(m) == 1) return SPMM_SCS;
     if (m.kernel == SPMV_KERNEL_BSR && m.has_bsr()) return SPMM_BSR;
     if (m.kernel == SPMV_KERNEL_SELLP && m.has_sellp() && m.sellp_seg_slc.size() <= 2 &&
         (sL == 1 || sL == 2 || sL == 4 || sL == 8 || sL == 16 || sL == 32 || sL == 64) &&

@@ -749,7 +749,8 @@ void spmm_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t 
         spmm_stream(m, x, ldx, y, ldy, k, mode, epi, s);
         return;
     }
-    // wave-per-row and the wide grid-transfer classes: no k-wide kernel
+    // wave-per-row, the wide grid-transfer classes and x-staged classes with eight
+    // lanes per row: no k-wide kernel
     for (int64_t c = 0; c < k; c++) {
         SpmvEpi e;
         e.b = epi.b ? epi.b + c * epi.ldb : nullptr;

@@ -94,6 +94,7 @@ SIGNATURES = {
     "amg_csr_set_grid": (i32, [vp, i64, i64, i64]),
     "amg_csr_spmv_epilogue": (i32, [vp, i32, vp, vp, vp, vp]),
     "amg_csr_grid_info": (i32, [vp, vp]),
+    "amg_csr_row_lanes": (i32, [vp, P(i64)]),
     "amg_grid_from_offsets": (i32, [vp, i64, i64, vp, P(i32)]),
     "amg_set_flag": (i32, [i32, i64]),
     "amg_source_hash": (C.c_char_p, []),
@@ -497,6 +498,9 @@ class SparseMatOp(LinOp):
         if d["xstaged"]:
             d["tile"], d["halo"] = tuple(int(v) for v in g[4:7]), tuple(int(v) for v in g[7:10])
             d["tile_source"] = ("none", "table", "timed", "env", "rule")[int(g[12])]
+        rl = i64()
+        _ck(_lib.amg_csr_row_lanes(self.h, C.byref(rl)))
+        d["row_lanes"] = rl.value
         return d
 
     def spmv_epilogue(self, mode, x, y, b=None, d=None):

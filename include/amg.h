@@ -195,8 +195,9 @@ amg_status amg_csr_spmv_epilogue(const amg_linop *op, int32_t mode, const double
  * (DIA codes, stencil classes, 3x3 blocks, pattern SELL, fp64 SELL-64, x-staged
  * SELL) read the matrix once per 8 columns with the epilogue fused at the
  * store; CSR-stream, value-coded SELL-64 and the 8-bit grid-transfer classes
- * have k-wide launches of their single-vector row sums; wave-per-row and the
- * wide grid-transfer classes run one SpMV per column.  X != Y; k >= 0; AMG_ERR_INVALID for a leading dimension below the
+ * have k-wide launches of their single-vector row sums; wave-per-row, the
+ * wide grid-transfer classes and x-staged stencil classes with eight lanes per
+ * row (amg_csr_row_lanes) run one SpMV per column.  X != Y; k >= 0; AMG_ERR_INVALID for a leading dimension below the
  * rows it spans. */
 amg_status amg_csr_spmm_epilogue(const amg_linop *op, int32_t mode, const double *X, int64_t ldx, double *Y,
                                  int64_t ldy, const double *B, int64_t ldb, const double *d, int64_t k);
@@ -206,6 +207,11 @@ amg_status amg_csr_spmm_epilogue(const amg_linop *op, int32_t mode, const double
  * gtx.hip), how the x-staged tile was chosen (1 the frozen per-shape table of
  * tuning.cpp, 2 timed at setup, 3 FAMG_XSCS_TILE)}. */
 amg_status amg_csr_grid_info(const amg_linop *op, int64_t *info12);
+/* Lanes that share one row sum of the x-staged stencil-class kernel: 8 on few
+ * long rows (fewer than 131072 rows, at least 256 padded offsets, 16-bit class
+ * ids: eight partial chains and a fixed three-step tree per row), else 1 (one
+ * sequential chain per row, the CSR order) -- also for every other storage. */
+amg_status amg_csr_row_lanes(const amg_linop *op, int64_t *lanes);
 
 /* Copy a host CSR with usize-compatible (int64) row pointers and column indices
  * and fp64 values to the device.  Columns must be sorted ascending within each

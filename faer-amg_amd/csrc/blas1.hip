@@ -7,6 +7,7 @@
 // tree) so repeated solves are bitwise reproducible.
 #include <algorithm>
 
+#include "block_sum.hpp"
 #include "famg.hpp"
 
 namespace famg {
@@ -122,18 +123,7 @@ void vec_nn_step(double *x, const double *d, const double *r, int64_t n, hipStre
 
 // ---------------------------------------------------------------- reductions
 
-constexpr int RED_GRID = VEC_DOT_PARTIALS;
-
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < (int)(blockDim.x >> 6); k++) t += sh[k];
-    return t;
-}
+constexpr int RED_GRID = VEC_DOT_PARTIALS;  // block_sum: block_sum.hpp (shared with pcg.hip)
 
 __global__ __launch_bounds__(256) void k_dot_partial(const double *x, const double *y, int64_t n,
                                                      double *partials) {

@@ -479,6 +479,27 @@ constexpr int VEC_DOT_PARTIALS = 1024;
 void vec_dot_dev(const double *x, const double *y, int64_t n, double *res, double *partials, hipStream_t s);
 double vec_dot(const double *x, const double *y, int64_t n, Ctx &ctx);  // syncs
 
+// k-wide vector kernels of the block solve drivers (pcg.hip): column-major blocks,
+// one launch over k columns, every column bitwise the single-vector kernel above.
+// partials: k * VEC_DOT_PARTIALS doubles, laid out [column][VEC_DOT_PARTIALS].
+// partials[c] = the block sums of x_c . y_c (vec_dot's first launch per column)
+void cg_dot_cols(const double *x, int64_t ldx, const double *y, int64_t ldy, int64_t n, int64_t k, double *partials,
+                 hipStream_t s);
+// t_c = vec_dot's second launch on partials[c], then on the device, per column:
+// ALPHA a_c = b_c / t_c;  STORE a_c = t_c (b unused);  BETA a_c = t_c / b_c, b_c = t_c
+enum CgFinal : int { CG_FINAL_ALPHA = 0, CG_FINAL_STORE = 1, CG_FINAL_BETA = 2 };
+void cg_final_cols(CgFinal op, const double *partials, double *a, double *b, int64_t k, hipStream_t s);
+// x_c += alpha_c p_c (vec_axpy) on column map[c] of X; r_c += (-alpha_c) Ap_c (vec_axpy);
+// partials[c] = the block sums of the new r_c . r_c -- one pass (P, AP, R: leading dimension ldw)
+void cg_update_cols(double *X, int64_t ldx, const int32_t *map, const double *P, const double *AP, double *R,
+                    int64_t ldw, const double *alpha, int64_t n, int64_t k, double *partials, hipStream_t s);
+// p_c = z_c + beta_c p_c (vec_xpay), beta on the device
+void cg_xpay_cols(double *P, int64_t ldp, const double *Z, int64_t ldz, const double *beta, int64_t n, int64_t k,
+                  hipStream_t s);
+// x_c += z_c (vec_add_inplace) on column map[c] of X
+void cg_add_cols(double *X, int64_t ldx, const int32_t *map, const double *Z, int64_t ldz, int64_t n, int64_t k,
+                 hipStream_t s);
+
 // marker kernel for rocprofv3 traces (amg_trace_mark)
 void trace_mark(Ctx &ctx, int32_t tag);
 

@@ -89,6 +89,233 @@ int64_t pcg_impl(const SolveOps &o, const double *b, double *x, int64_t max_iter
     return it;
 }
 
+// ------------------------------------------------------- block solve drivers
+
+namespace {
+
+// pinned host memory for the per-iteration copies (freed when the call ends)
+template <typename T> struct PinnedBuf {
+    T *p = nullptr;
+    explicit PinnedBuf(size_t n) { FAMG_CHECK_HIP(hipHostMalloc((void **)&p, std::max<size_t>(1, n) * sizeof(T))); }
+    ~PinnedBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+};
+
+// the workspace of one block solve, allocated once per call: nblk blocks of
+// n x kmax (leading dimension n), the dots' partials, the per-slot scalars
+// (alpha, beta, rz, and two rows of results the host copies) and the slot map
+struct BlockWs {
+    int64_t kmax, ld;
+    DevBuf<double> blocks, scal;
+    DevBuf<int32_t> map;
+    PinnedBuf<double> h_res;
+    PinnedBuf<int32_t> h_map;
+    BlockWs(int64_t n, int64_t k, int nblk)
+        : kmax(std::min<int64_t>(k, MG_BLOCK_COLS)), ld(std::max<int64_t>(1, n)),
+          blocks((size_t)nblk * ld * kmax), scal((size_t)kmax * (VEC_DOT_PARTIALS + 5)), map((size_t)kmax),
+          h_res(2 * (size_t)kmax), h_map((size_t)kmax) {}
+    double *block(int b) const { return blocks.get() + (size_t)b * ld * kmax; }
+    double *partials() const { return scal.get(); }
+    double *alpha() const { return scal.get() + kmax * VEC_DOT_PARTIALS; }
+    double *beta() const { return alpha() + kmax; }
+    double *rz() const { return beta() + kmax; }
+    double *res() const { return rz() + kmax; }  // 2 * kmax
+    // the first na entries of the host map to the device (the host copy is only
+    // rewritten after a stream synchronise, so the copy has left it by then)
+    void upload_map(int64_t na, hipStream_t s) const {
+        if (na > 0)
+            FAMG_CHECK_HIP(hipMemcpyAsync(map.get(), h_map.p, na * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    // cnt results to the host, then wait: the one host round trip of an iteration
+    void fetch(int64_t cnt, hipStream_t s) const {
+        FAMG_CHECK_HIP(hipMemcpyAsync(h_res.p, res(), cnt * sizeof(double), hipMemcpyDeviceToHost, s));
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+    }
+};
+
+// OUT (ld n) = B - A X over kw columns, as residual() does per column
+void residual_block(LinOp &A, CsrOp *a, double *out, int64_t ldo, const double *B, int64_t ldb, const double *X,
+                    int64_t ldx, int64_t kw) {
+    hipStream_t s = A.ctx->stream;
+    if (a) {
+        spmm_epi(a->m, X, ldx, out, ldo, kw, SPMV_RESID, SpmmEpi{B, ldb, nullptr}, s);
+        return;
+    }
+    A.apply_block(out, ldo, X, ldx, kw);
+    vec_sub_cols(out, ldo, B, ldb, out, ldo, A.nrows, kw, s);
+}
+
+}  // namespace
+
+void pcg_block_impl(LinOp &A, LinOp *M, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k,
+                    int64_t max_iter, double rel_tol, double abs_tol, double *hist, int64_t ld_hist, int64_t *iters) {
+    if (k <= 0) return;
+    hipStream_t s = A.ctx->stream;
+    const int64_t n = A.nrows;
+    BlockWs w(n, k, 4);
+    const int64_t ld = w.ld;
+    double *R = w.block(0), *Z = w.block(1), *P = w.block(2), *AP = w.block(3);
+    double *Zp = M ? Z : R;  // identity preconditioner: z is r itself
+    auto *a = dynamic_cast<CsrOp *>(&A);
+    std::vector<int64_t> col(w.kmax);  // slot -> column of the chunk
+    std::vector<double> bn(w.kmax), tol(w.kmax);
+    std::vector<char> stop(w.kmax);
+    for (int64_t c0 = 0; c0 < k; c0 += MG_BLOCK_COLS) {
+        const int64_t kw = std::min<int64_t>(MG_BLOCK_COLS, k - c0);
+        const double *Bc = B + c0 * ldb;
+        double *Xc = X + c0 * ldx;
+        double *histc = hist ? hist + c0 * ld_hist : nullptr;
+        int64_t *itc = iters + c0;
+        int64_t na = kw;  // active slots [0, na)
+        // slot s takes the last active slot's column (R, and P / rz once they live)
+        auto drop = [&](int64_t sl, bool live) {
+            const int64_t last = na - 1;
+            if (sl != last) {
+                vec_copy(R + sl * ld, R + last * ld, n, s);
+                if (live) {
+                    vec_copy(P + sl * ld, P + last * ld, n, s);
+                    FAMG_CHECK_HIP(hipMemcpyAsync(w.rz() + sl, w.rz() + last, sizeof(double), hipMemcpyDeviceToDevice, s));
+                }
+                col[sl] = col[last];
+                bn[sl] = bn[last];
+                tol[sl] = tol[last];
+                w.h_map.p[sl] = w.h_map.p[last];
+            }
+            na--;
+        };
+        // descending, so the slot moved in has been looked at already
+        auto compact = [&](bool live) {
+            const int64_t before = na;
+            for (int64_t sl = before; sl-- > 0;)
+                if (stop[sl]) drop(sl, live);
+            if (na != before) w.upload_map(na, s);
+        };
+        for (int64_t sl = 0; sl < kw; sl++) {
+            col[sl] = sl;
+            w.h_map.p[sl] = (int32_t)sl;
+        }
+        w.upload_map(kw, s);
+        residual_block(A, a, R, ld, Bc, ldb, Xc, ldx, kw);
+        cg_dot_cols(Bc, ldb, Bc, ldb, n, kw, w.partials(), s);
+        cg_final_cols(CG_FINAL_STORE, w.partials(), w.res(), nullptr, kw, s);
+        cg_dot_cols(R, ld, R, ld, n, kw, w.partials(), s);
+        cg_final_cols(CG_FINAL_STORE, w.partials(), w.res() + kw, nullptr, kw, s);
+        w.fetch(2 * kw, s);
+        for (int64_t sl = 0; sl < kw; sl++) {
+            bn[sl] = std::sqrt(w.h_res.p[sl]);
+            tol[sl] = std::max(rel_tol * bn[sl], abs_tol);
+            stop[sl] = !(std::sqrt(w.h_res.p[kw + sl]) > tol[sl]);
+            if (stop[sl]) itc[sl] = 0;
+        }
+        compact(false);
+        if (na == 0) continue;
+        if (M) M->apply_block(Z, ld, R, ld, na);
+        vec_copy_cols(P, ld, Zp, ld, n, na, s);
+        cg_dot_cols(R, ld, Zp, ld, n, na, w.partials(), s);
+        cg_final_cols(CG_FINAL_STORE, w.partials(), w.rz(), nullptr, na, s);
+        for (int64_t it = 1; it <= max_iter && na > 0; it++) {
+            if (a) spmm_epi(a->m, P, ld, AP, ld, na, SPMV_SET, SpmmEpi{}, s);
+            else A.apply_block(AP, ld, P, ld, na);
+            cg_dot_cols(P, ld, AP, ld, n, na, w.partials(), s);
+            cg_final_cols(CG_FINAL_ALPHA, w.partials(), w.alpha(), w.rz(), na, s);
+            cg_update_cols(Xc, ldx, w.map.get(), P, AP, R, ld, w.alpha(), n, na, w.partials(), s);
+            cg_final_cols(CG_FINAL_STORE, w.partials(), w.res(), nullptr, na, s);
+            w.fetch(na, s);
+            for (int64_t sl = 0; sl < na; sl++) {
+                const double rn = std::sqrt(w.h_res.p[sl]);
+                if (histc) histc[col[sl] * ld_hist + it - 1] = rn / bn[sl];
+                stop[sl] = rn <= tol[sl];
+                if (stop[sl]) itc[col[sl]] = it;
+            }
+            compact(true);
+            if (na == 0 || it == max_iter) break;  // the last iteration's z, beta and p are never read
+            if (M) M->apply_block(Z, ld, R, ld, na);
+            cg_dot_cols(R, ld, Zp, ld, n, na, w.partials(), s);
+            cg_final_cols(CG_FINAL_BETA, w.partials(), w.beta(), w.rz(), na, s);
+            cg_xpay_cols(P, ld, Zp, ld, w.beta(), n, na, s);
+        }
+        for (int64_t sl = 0; sl < na; sl++) itc[col[sl]] = max_iter + 1;
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+    }
+}
+
+void stationary_block_impl(LinOp &A, LinOp &M, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k,
+                           int64_t max_iter, double rel_tol, double *hist, int64_t ld_hist, int64_t *iters) {
+    if (k <= 0) return;
+    hipStream_t s = A.ctx->stream;
+    const int64_t n = A.nrows;
+    BlockWs w(n, k, 2);
+    const int64_t ld = w.ld;
+    double *R = w.block(0), *Z = w.block(1);
+    auto *a = dynamic_cast<CsrOp *>(&A);
+    // Nothing but X carries over from sweep to sweep, so the slots stay in column
+    // order: a column that stops is closed up (R's columns behind it move down
+    // one) and R = B - A X runs as one SpMM per run of adjacent active columns.
+    std::vector<int64_t> col(w.kmax);
+    std::vector<double> bn(w.kmax);
+    std::vector<char> stop(w.kmax);
+    for (int64_t c0 = 0; c0 < k; c0 += MG_BLOCK_COLS) {
+        const int64_t kw = std::min<int64_t>(MG_BLOCK_COLS, k - c0);
+        const double *Bc = B + c0 * ldb;
+        double *Xc = X + c0 * ldx;
+        double *histc = hist ? hist + c0 * ld_hist : nullptr;
+        int64_t *itc = iters + c0;
+        int64_t na = kw;
+        for (int64_t sl = 0; sl < kw; sl++) {
+            col[sl] = sl;
+            w.h_map.p[sl] = (int32_t)sl;
+        }
+        w.upload_map(kw, s);
+        cg_dot_cols(Bc, ldb, Bc, ldb, n, kw, w.partials(), s);
+        cg_final_cols(CG_FINAL_STORE, w.partials(), w.res(), nullptr, kw, s);
+        w.fetch(kw, s);
+        for (int64_t sl = 0; sl < kw; sl++) bn[sl] = std::sqrt(w.h_res.p[sl]);
+        for (int64_t it = 1; na > 0; it++) {
+            for (int64_t s0 = 0; s0 < na;) {
+                int64_t s1 = s0 + 1;
+                while (s1 < na && col[s1] == col[s1 - 1] + 1) s1++;
+                residual_block(A, a, R + s0 * ld, ld, Bc + col[s0] * ldb, ldb, Xc + col[s0] * ldx, ldx, s1 - s0);
+                s0 = s1;
+            }
+            cg_dot_cols(R, ld, R, ld, n, na, w.partials(), s);
+            cg_final_cols(CG_FINAL_STORE, w.partials(), w.res(), nullptr, na, s);
+            w.fetch(na, s);
+            bool any = false;
+            for (int64_t sl = 0; sl < na; sl++) {
+                const double rel = std::sqrt(w.h_res.p[sl]) / bn[sl];
+                if (histc) histc[col[sl] * ld_hist + it - 1] = rel;
+                stop[sl] = rel < rel_tol || it >= max_iter;
+                if (stop[sl]) {
+                    itc[col[sl]] = it;
+                    any = true;
+                }
+            }
+            if (any) {
+                int64_t dst = 0;
+                for (int64_t sl = 0; sl < na; sl++) {
+                    if (stop[sl]) continue;
+                    if (dst != sl) {
+                        vec_copy(R + dst * ld, R + sl * ld, n, s);
+                        col[dst] = col[sl];
+                        bn[dst] = bn[sl];
+                        w.h_map.p[dst] = w.h_map.p[sl];
+                    }
+                    dst++;
+                }
+                na = dst;
+                w.upload_map(na, s);
+            }
+            if (na == 0) break;
+            M.apply_block(Z, ld, R, ld, na);
+            cg_add_cols(Xc, ldx, w.map.get(), Z, ld, n, na, s);
+        }
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+    }
+}
+
 void CompositeOp::apply(double *out, const double *rhs) {
     std::lock_guard<std::mutex> lk(mtx);
     hipStream_t s = ctx->stream;
@@ -166,6 +393,31 @@ SolveOps single_gpu_ops(LinOp &a, LinOp *m) {
     return o;
 }
 
+// the block drivers' argument checks that need no handle (before the handle
+// checks, as in amg_adaptive_build) ...
+void block_solve_args(const double *B, const double *X, int64_t k, const double *hist, int64_t ld_hist,
+                      int64_t max_iter, const int64_t *iters) {
+    FAMG_REQUIRE(B && X && iters, AMG_ERR_INVALID, "block solve: null B, X or iters");
+    FAMG_REQUIRE(k >= 0, AMG_ERR_INVALID, "block solve: negative column count");
+    FAMG_REQUIRE(!hist || ld_hist >= max_iter, AMG_ERR_INVALID, "block solve: ld_hist below max_iter");
+    FAMG_REQUIRE(B != X, AMG_ERR_INVALID, "block solve: B must not alias X");
+}
+
+// ... and the ones that need the operators
+void block_solve_ops(LinOp &a, LinOp *m, const double *B, int64_t ldb, const double *X, int64_t ldx, int64_t k) {
+    auto dist = [](const LinOp &o) { return o.kind() == Kind::DistCsr || o.kind() == Kind::DistMultigrid; };
+    FAMG_REQUIRE(!dist(a) && !(m && dist(*m)), AMG_ERR_UNSUPPORTED,
+                 "block solve: distributed operators have no block cycle (amg_dist_pcg_solve per column)");
+    FAMG_REQUIRE(a.nrows == a.ncols && (!m || (m->nrows == a.nrows && m->ncols == a.nrows)), AMG_ERR_DIM,
+                 "solver dims");
+    const int64_t n = a.nrows;
+    FAMG_REQUIRE(ldb >= n && ldx >= n, AMG_ERR_INVALID, "block solve: leading dimension too small");
+    if (k > 0 && n > 0) {  // the two blocks' extents must not overlap
+        const double *be = B + (k - 1) * ldb + n, *xe = X + (k - 1) * ldx + n;
+        FAMG_REQUIRE(be <= X || xe <= B, AMG_ERR_INVALID, "block solve: B must not alias X");
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -231,6 +483,36 @@ amg_status amg_pcg_solve(amg_linop *A, amg_linop *M, const double *b, double *x,
         FAMG_REQUIRE(a.nrows == a.ncols && (!m || m->nrows == a.nrows), AMG_ERR_DIM, "solver dims");
         a.ctx->set_device();
         *iters = pcg_impl(single_gpu_ops(a, m), b, x, max_iter, rel_tol, abs_tol, hist);
+    });
+}
+
+amg_status amg_pcg_solve_block(amg_linop *A, amg_linop *M, const double *B, int64_t ldb, double *X, int64_t ldx,
+                               int64_t k, int64_t max_iter, double rel_tol, double abs_tol, double *hist,
+                               int64_t ld_hist, int64_t *iters) {
+    return guard([&] {
+        block_solve_args(B, X, k, hist, ld_hist, max_iter, iters);
+        FAMG_REQUIRE(max_iter >= 0, AMG_ERR_INVALID, "block solve: negative max_iter");
+        LinOp &a = need_op(A);
+        LinOp *m = M ? &need_op(M) : nullptr;
+        block_solve_ops(a, m, B, ldb, X, ldx, k);
+        if (k == 0) return;
+        a.ctx->set_device();
+        pcg_block_impl(a, m, B, ldb, X, ldx, k, max_iter, rel_tol, abs_tol, hist, ld_hist, iters);
+    });
+}
+
+amg_status amg_stationary_solve_block(amg_linop *A, amg_linop *M, const double *B, int64_t ldb, double *X,
+                                      int64_t ldx, int64_t k, int64_t max_iter, double rel_tol, double *hist,
+                                      int64_t ld_hist, int64_t *iters) {
+    return guard([&] {
+        block_solve_args(B, X, k, hist, ld_hist, max_iter, iters);
+        FAMG_REQUIRE(max_iter > 0, AMG_ERR_INVALID, "block solve: max_iter must be positive");
+        LinOp &a = need_op(A);
+        LinOp &m = need_op(M);
+        block_solve_ops(a, &m, B, ldb, X, ldx, k);
+        if (k == 0) return;
+        a.ctx->set_device();
+        stationary_block_impl(a, m, B, ldb, X, ldx, k, max_iter, rel_tol, hist, ld_hist, iters);
     });
 }
 

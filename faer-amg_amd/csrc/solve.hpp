@@ -36,6 +36,23 @@ int64_t stationary_impl(const SolveOps &o, const double *b, double *x, int64_t m
 int64_t pcg_impl(const SolveOps &o, const double *b, double *x, int64_t max_iter, double rel_tol, double abs_tol,
                  double *hist);
 
+// The two loops over k right-hand sides at once (single GPU; B, X column-major
+// device blocks).  Every column runs its own recurrence -- unlike faer's
+// conjugate_gradient on an n x k rhs, which couples the columns -- and is bitwise
+// the single-vector loop above: A P / B - A X as one SpMM when A is a CSR matrix,
+// M through apply_block, the vector work in pcg.hip's k-wide kernels, alpha, beta
+// and r.z on the device.  Per iteration the host reads the active columns' r.r in
+// one copy and one stream synchronise, and does sqrt, history and the stopping
+// test as the single-vector loop does.  A column that stops is frozen (its X never
+// written again) and leaves the workspace, which stays compact: the SpMM, the
+// preconditioner and the vector kernels run over the active columns only.
+// Chunks of MG_BLOCK_COLS columns, one after another.  M null: identity (PCG only).
+// hist: max_iter x k column-major (ld_hist) or null; iters: k entries.
+void pcg_block_impl(LinOp &A, LinOp *M, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k,
+                    int64_t max_iter, double rel_tol, double abs_tol, double *hist, int64_t ld_hist, int64_t *iters);
+void stationary_block_impl(LinOp &A, LinOp &M, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k,
+                           int64_t max_iter, double rel_tol, double *hist, int64_t ld_hist, int64_t *iters);
+
 // Composite (preconditioners/composite.rs:11-83): components c_0..c_{m-1}
 // applied c_{m-1}, ..., c_1, c_0, c_1, ..., c_{m-1}; each step
 // out += c(r); r = rhs - A out, starting from out = 0, r = rhs.

@@ -210,6 +210,8 @@ SIGNATURES = {
     "amg_multigrid_block_plan": (i32, [vp, i64, vp, i64, P(i64)]),
     "amg_adaptive_config_default": (i32, [vp]),
     "amg_adaptive_build": (i32, [vp, vp, i64, i64, vp, vp, P(vp)]),
+    "amg_pcg_solve_block": (i32, [vp, vp, vp, i64, vp, i64, i64, i64, dbl, dbl, vp, i64, vp]),
+    "amg_stationary_solve_block": (i32, [vp, vp, vp, i64, vp, i64, i64, i64, dbl, vp, i64, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -1096,6 +1098,45 @@ def pcg_solve(A, M, b, x, max_iter=1000, rel_tol=1e-8, abs_tol=0.0):
                                vp(x.data_ptr()), max_iter, rel_tol, abs_tol,
                                hist.ctypes.data_as(vp), C.byref(it)))
     return it.value, hist[:min(it.value, max_iter)]
+
+
+def _solve_blocks(B, X):
+    """Pointers, k and leading dimensions of the column-major device blocks B, X."""
+    pb, memb, nb, kb, ldb = _dptr(B)
+    px, memx, nx, kx, ldx = _dptr(X)
+    if (nb, kb) != (nx, kx):
+        raise ValueError("B and X must have equal shapes")
+    if memb != AMG_MEM_DEVICE or memx != AMG_MEM_DEVICE:
+        raise ValueError("B and X must be device tensors")
+    return pb, ldb, px, ldx, kb
+
+
+def pcg_solve_block(A, M, B, X, max_iter=1000, rel_tol=1e-8, abs_tol=0.0):
+    """amg_pcg_solve_block: the k columns of B (column-major n x k device tensor,
+    stride(0) == 1) through pcg_solve's loop at once, X in/out.  Every column is
+    bitwise pcg_solve of that column (independent recurrences; the matrix and the
+    hierarchy are streamed once per 8 columns).  Returns (iters[k], [hist per column])."""
+    pb, ldb, px, ldx, k = _solve_blocks(B, X)
+    ldh = max(max_iter, 1)
+    hist = np.zeros((ldh, max(k, 1)), order="F")
+    iters = np.zeros(max(k, 1), np.int64)
+    with _ordered(A.ctx, AMG_MEM_DEVICE):
+        _ck(_lib.amg_pcg_solve_block(A.h, None if M is None else M.h, pb, ldb, px, ldx, k, max_iter, rel_tol,
+                                     abs_tol, hist.ctypes.data_as(vp), ldh, iters.ctypes.data_as(vp)))
+    return iters[:k], [hist[:min(int(iters[c]), max_iter), c].copy() for c in range(k)]
+
+
+def stationary_solve_block(A, M, B, X, max_iter=100, rel_tol=1e-8):
+    """amg_stationary_solve_block: stationary_solve on the k columns of B at once,
+    every column bitwise that call.  Returns (iters[k], [hist per column])."""
+    pb, ldb, px, ldx, k = _solve_blocks(B, X)
+    ldh = max(max_iter, 1)
+    hist = np.zeros((ldh, max(k, 1)), order="F")
+    iters = np.zeros(max(k, 1), np.int64)
+    with _ordered(A.ctx, AMG_MEM_DEVICE):
+        _ck(_lib.amg_stationary_solve_block(A.h, M.h, pb, ldb, px, ldx, k, max_iter, rel_tol,
+                                            hist.ctypes.data_as(vp), ldh, iters.ctypes.data_as(vp)))
+    return iters[:k], [hist[:int(iters[c]), c].copy() for c in range(k)]
 
 
 class BlockSmoother(LinOp):

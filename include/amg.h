@@ -624,6 +624,46 @@ amg_status amg_stationary_solve(amg_linop *A, amg_linop *M, const double *b, dou
 amg_status amg_pcg_solve(amg_linop *A, amg_linop *M, const double *b, double *x,
                          int64_t max_iter, double rel_tol, double abs_tol, double *hist,
                          int64_t *iters);
+/* k right-hand sides through the loop of amg_pcg_solve at once (the n x k
+ * `rhs: MatRef` of the reference's solve driver, utils.rs:553-633).  B, X:
+ * device, column-major n x k, leading dimensions ldb, ldx >= n; X in/out
+ * (initial guess).  Every column runs its own CG recurrence: column c's X,
+ * iters[c] and history are bitwise what amg_pcg_solve(A, M, B + c*ldb,
+ * X + c*ldx, ...) gives.  This deviates from the reference, whose faer
+ * conjugate_gradient couples the columns of an n x k rhs (one k x k system per
+ * iteration); independent columns are what keeps each one the single solve, as
+ * amg_linop_apply / amg_csr_spmm_epilogue already promise per column.
+ * A P and B - A X run as one SpMM per 8 columns when A is a CSR matrix; M
+ * through its block apply (a multigrid or a Composite: one block cycle, flag 11;
+ * a Diag: one k-wide scale; other kinds column by column); alpha, beta and r.z
+ * stay on the device.  Per iteration the host reads the active columns' r.r in
+ * one copy and one stream synchronise (amg_pcg_solve: three per column).  A
+ * column that has stopped -- converged, or started at or below its tolerance,
+ * which a zero column with a zero guess does -- is frozen: its X is not written
+ * again and the SpMM, the preconditioner and the vector kernels run over the
+ * remaining columns only.  Chunks of 32 columns, one after another.
+ * hist: host, max_iter x k column-major (ld_hist >= max_iter), may be NULL;
+ * column c gets min(iters[c], max_iter) entries.  iters: host, k entries, each
+ * as amg_pcg_solve's (0: the start residual is within tolerance; max_iter + 1:
+ * not converged).  M may be NULL (identity).  k = 0 returns AMG_OK and touches
+ * nothing.  AMG_ERR_INVALID: null B, X or iters, k < 0, max_iter < 0, hist with
+ * ld_hist < max_iter, B aliasing X (the blocks' extents must not overlap), a
+ * null handle, a leading dimension below n; the checks that need no handle come
+ * first.  AMG_ERR_DIM as amg_pcg_solve.  AMG_ERR_UNSUPPORTED: a distributed
+ * operator or preconditioner -- the distributed multigrid has no block cycle;
+ * call amg_dist_pcg_solve per column. */
+amg_status amg_pcg_solve_block(amg_linop *A, amg_linop *M, const double *B, int64_t ldb,
+                               double *X, int64_t ldx, int64_t k, int64_t max_iter,
+                               double rel_tol, double abs_tol, double *hist, int64_t ld_hist,
+                               int64_t *iters);
+/* The same for amg_stationary_solve (M required, max_iter > 0): per sweep
+ * R = B - A X over the active columns, their norms to the host in one copy,
+ * Z = M R as a block, X += Z.  Column c's X, iters[c] and history are bitwise
+ * amg_stationary_solve's; a column stops below rel_tol or at max_iter. */
+amg_status amg_stationary_solve_block(amg_linop *A, amg_linop *M, const double *B, int64_t ldb,
+                                      double *X, int64_t ldx, int64_t k, int64_t max_iter,
+                                      double rel_tol, double *hist, int64_t ld_hist,
+                                      int64_t *iters);
 
 /* ---- multi-GPU (row-block partition + RCCL halo exchange) ------- */
 

@@ -727,6 +727,51 @@ amg_status amg_sgs_info(const amg_linop *op, int64_t *info4) {
     });
 }
 
+amg_status amg_chebyshev_config_default(amg_chebyshev_config *cfg) {
+    return guard([&] {
+        FAMG_REQUIRE(cfg, AMG_ERR_INVALID, "null config");
+        const ChebyConfig d;
+        cfg->steps = d.steps;
+        cfg->eig_iters = d.eig_iters;
+        cfg->eig_ratio = d.eig_ratio;
+        cfg->boost = d.boost;
+        cfg->lambda_max = d.lambda_max;
+    });
+}
+
+amg_status amg_chebyshev_create(const amg_linop *A, const amg_chebyshev_config *cfg, amg_linop **out) {
+    return guard([&] {
+        // argument checks, before anything touches a device
+        FAMG_REQUIRE(out, AMG_ERR_INVALID, "null output");
+        auto a = need_csr(A);
+        ChebyConfig c;
+        if (cfg) {
+            c.steps = cfg->steps;
+            c.eig_iters = cfg->eig_iters;
+            c.eig_ratio = cfg->eig_ratio;
+            c.boost = cfg->boost;
+            c.lambda_max = cfg->lambda_max;
+        }
+        chebyshev_check(c);
+        a->ctx->set_device();
+        *out = box(make_chebyshev(a, c));
+    });
+}
+
+amg_status amg_chebyshev_info(const amg_linop *op, double *info6) {
+    return guard([&] {
+        FAMG_REQUIRE(info6, AMG_ERR_INVALID, "null output");
+        auto p = std::dynamic_pointer_cast<ChebyOp>(need(op).shared_from_this());
+        FAMG_REQUIRE(p, AMG_ERR_INVALID, "operator is not a Chebyshev smoother");
+        info6[0] = p->lambda_max;
+        info6[1] = p->lambda_min;
+        info6[2] = (double)p->steps;
+        info6[3] = p->ritz;
+        info6[4] = p->row_bound;
+        info6[5] = (double)p->eig_run;
+    });
+}
+
 amg_status amg_coarse_chol_create(const amg_linop *A, amg_linop **out) {
     return guard([&] {
         FAMG_REQUIRE(out, AMG_ERR_INVALID, "null output");
@@ -1121,6 +1166,8 @@ amg_status amg_adaptive_build(amg_linop *A, const double *X0, int64_t ld, int64_
         c.max_levels = cfg->sa.max_levels;
         c.omega = cfg->sa.omega;
         c.smoother = cfg->sa.smoother;
+        FAMG_REQUIRE(cfg->sa.chebyshev_steps >= 0, AMG_ERR_INVALID, "sa config: negative chebyshev_steps");
+        c.chebyshev_steps = cfg->sa.chebyshev_steps;
         DevBuf<double> X(n * dim);
         std::vector<double> basis(n * dim), w(dim);
         auto upload_x0 = [&] {

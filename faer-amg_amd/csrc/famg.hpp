@@ -6,6 +6,7 @@
 //   CsrOp            <- SparseMatOp / ParSpmmOp / SparseRowMat (core.rs, par_spmm.rs)
 //   DiagOp           <- Diag<f64> from new_jacobi/new_l1/new_l2 (smoothers.rs:43-86)
 //   SgsOp            <- SmootherKind::SymGaussSeidel (smoothers.rs:20, unimplemented there)
+//   ChebyOp          <- no counterpart: a Chebyshev polynomial smoother
 //   CoarseCholOp     <- SparseCholeskySolve (coarse_solvers.rs:164-276)
 //   MultigridOp      <- Multigrid (preconditioners/multigrid.rs:171-518)
 // All operator data lives in HBM; apply() works on device pointers and is
@@ -548,7 +549,8 @@ enum class Kind : int {
     DistCsr = AMG_KIND_DIST_CSR,
     DistMultigrid = AMG_KIND_DIST_MULTIGRID,
     Composite = AMG_KIND_COMPOSITE,
-    Block = AMG_KIND_BLOCK
+    Block = AMG_KIND_BLOCK,
+    Chebyshev = AMG_KIND_CHEBYSHEV
 };
 
 struct LinOp : std::enable_shared_from_this<LinOp> {
@@ -628,6 +630,38 @@ struct SgsOp : LinOp {
     void first_color(double *e, const double *r);
     void apply(double *out, const double *rhs) override;
     void apply_in_place(double *rhs) override;
+};
+
+// Chebyshev polynomial smoother (cheby.hip): z = S b is `steps` terms
+// of the Chebyshev iteration on D^-1 A over [lambda_max / eig_ratio, lambda_max]
+// from z = 0 -- steps - 1 products with A (SPMV_RESID) and one fused vector pass
+// per term.  Symmetric; k-wide (apply is k = 1 of apply_block's kernels).
+struct ChebyConfig {
+    int64_t steps = 2;      // m >= 1
+    int64_t eig_iters = 10; // Lanczos steps, 0..64; 0 = the row-sum bound G alone
+    double eig_ratio = 20.0, boost = 1.1;
+    double lambda_max = 0.0;  // > 0: the caller's bound, nothing estimated
+};
+struct ChebyOp : LinOp {
+    CsrPtr A;
+    DevBuf<double> dinv;         // 1 / a_ii
+    std::vector<double> c1, c2;  // per term (c1[0] unused), computed once on the host
+    int64_t steps = 0, eig_run = 0;
+    double lambda_max = 0.0, lambda_min = 0.0;
+    double ritz = 0.0, row_bound = 0.0;  // the Lanczos Ritz value / G (0: not computed)
+    Kind kind() const override { return Kind::Chebyshev; }
+    bool is_precond() const override { return true; }
+    // launches on ctx->stream only, never allocates, never synchronises (graph capture)
+    void apply(double *out, const double *rhs) override;
+    // chunks of MG_BLOCK_COLS columns; A read once per 8 columns (spmm_epi)
+    void apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) override;
+
+  private:
+    friend std::shared_ptr<ChebyOp> make_chebyshev(const CsrPtr &A, const ChebyConfig &cfg);
+    DevBuf<double> r0_, r1_, d_;     // single-vector workspace, allocated at creation
+    DevBuf<double> br0_, br1_, bd_;  // n x kw block workspace (first block apply, grown on demand)
+    void run(double *X, int64_t ldx, const double *B, int64_t ldb, int64_t kw, double *R0, double *R1, double *D,
+             int64_t ldw, bool single);
 };
 
 struct CoarseCholOp : LinOp {
@@ -806,6 +840,10 @@ void sgs27_setup(SgsOp &S);
 bool sgs27_applies(const SgsOp &S, const double *x, const double *b);  // fused and 16-B aligned vectors
 void sgs27_sweep(SgsOp &S, double *x, const double *b, bool zero);
 std::shared_ptr<CoarseCholOp> make_coarse_chol(CsrOp &A);
+// AMG_ERR_INVALID for config values out of range (chebyshev_check: host only),
+// AMG_ERR_DIM for a non-square A, AMG_ERR_NOT_SPD for a diagonal entry <= 0
+void chebyshev_check(const ChebyConfig &cfg);
+std::shared_ptr<ChebyOp> make_chebyshev(const CsrPtr &A, const ChebyConfig &cfg);
 
 // SA setup pieces
 CsrPtr sa_tentative(Ctx *ctx, int64_t n, const int64_t *agg_of, int64_t naggs,
@@ -869,6 +907,7 @@ struct SaConfig {
     int64_t coarsest_dim = 1000, max_levels = 0;
     double omega = 0.66;
     int smoother = 1;
+    int chebyshev_steps = 0;  // smoother 4: steps per application (0 = ChebyConfig's default)
 };
 struct SaLevelInfo {
     int64_t n, block_size, nodes, aggregates, strength_edges;

@@ -507,6 +507,7 @@ void MultigridOp::smooth(int64_t l, double *&v, double *&t, const double *f, boo
     auto *A = dynamic_cast<CsrOp *>(L.A.get());
     auto *D = dynamic_cast<DiagOp *>(L.S.get());
     auto *G = dynamic_cast<SgsOp *>(L.S.get());
+    auto *C = dynamic_cast<ChebyOp *>(L.S.get());
     log_at(l, AMG_ROLE_SMOOTH);
     for (int64_t it = 0; it < steps; it++) {
         const bool zero = v_zero && it == 0;
@@ -537,6 +538,16 @@ void MultigridOp::smooth(int64_t l, double *&v, double *&t, const double *f, boo
                 vec_add_inplace(v, t, n, s);
             } else {
                 G->sweep_x(v, f);  // fused: x <- x + SGS(f - A x)
+            }
+        } else if (A && C) {
+            if (zero) {
+                C->apply(v, f);  // v = 0 + S (f - A 0)
+            } else {  // the literal form with one RESID launch: r = f - A v, v += S r
+                SpmvEpi epi;
+                epi.b = f;
+                spmv(A->m, v, L.r.get(), SPMV_RESID, epi, s);
+                C->apply(t, L.r.get());
+                vec_add_inplace(v, t, n, s);
             }
         } else {
             if (zero) {
@@ -911,8 +922,9 @@ void MultigridOp::ensure_block_workspace(int64_t kw) {
     }
 }
 
-// smooth() on a block: Jacobi ping-pongs between (V, ldv) and (T, ldt); SGS and
-// every other smoother run per column on V (their level's A k-wide where they need it)
+// smooth() on a block: Jacobi ping-pongs between (V, ldv) and (T, ldt); Chebyshev is
+// k-wide (ChebyOp::apply_block); SGS and every other smoother run per column on V
+// (their level's A k-wide where they need it)
 void MultigridOp::block_smooth(int64_t l, double *&V, int64_t &ldv, double *&T, int64_t &ldt, const double *F,
                                int64_t ldf, int64_t kw, bool v_zero) {
     MgLevel &L = levels[l];
@@ -921,6 +933,7 @@ void MultigridOp::block_smooth(int64_t l, double *&V, int64_t &ldv, double *&T, 
     auto *A = dynamic_cast<CsrOp *>(L.A.get());
     auto *D = dynamic_cast<DiagOp *>(L.S.get());
     auto *G = dynamic_cast<SgsOp *>(L.S.get());
+    auto *C = dynamic_cast<ChebyOp *>(L.S.get());
     log_at(l, AMG_ROLE_SMOOTH);
     for (int64_t it = 0; it < steps; it++) {
         const bool zero = v_zero && it == 0;
@@ -938,6 +951,14 @@ void MultigridOp::block_smooth(int64_t l, double *&V, int64_t &ldv, double *&T, 
                 vec_add_cols(V, ldv, T, ldt, n, kw, s);
             } else {
                 for (int64_t c = 0; c < kw; c++) G->sweep_x(V + c * ldv, F + c * ldf);
+            }
+        } else if (A && C) {  // k-wide throughout: nothing per column
+            if (zero) {
+                C->apply_block(V, ldv, F, ldf, kw);
+            } else {
+                spmm_epi(A->m, V, ldv, L.br.get(), n, kw, SPMV_RESID, SpmmEpi{F, ldf, nullptr}, s);
+                C->apply_block(T, ldt, L.br.get(), n, kw);
+                vec_add_cols(V, ldv, T, ldt, n, kw, s);
             }
         } else {
             if (zero) {
@@ -1312,6 +1333,7 @@ std::shared_ptr<MultigridOp> sa_build_box(const CsrPtr &A, int64_t nx, int64_t n
         }
         case 3:  // BlockSmoother over the level's box aggregates (block_smoothers.rs)
             return make_block_smoother(*M, aggs[l].data(), naggs[l], 1);
+        case 4: return make_chebyshev(M, ChebyConfig{});  // the defaults
         default: fail(AMG_ERR_INVALID, "unknown smoother kind");
         }
     };

@@ -667,6 +667,11 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
         }
         case 3:  // BlockSmoother over the level's aggregates (block_smoothers.rs)
             return make_block_smoother(*M, aggs[l].data(), naggs[l], bss[l]);
+        case 4: {  // Chebyshev (cheby.hip), its other parameters at their defaults
+            ChebyConfig cc;
+            if (cfg.chebyshev_steps > 0) cc.steps = cfg.chebyshev_steps;
+            return make_chebyshev(M, cc);
+        }
         default: fail(AMG_ERR_INVALID, "unknown smoother kind");
         }
     };
@@ -731,6 +736,8 @@ amg_status amg_sa_build(amg_linop *A, const double *near_null, int64_t ld, int64
         c.max_levels = cfg->max_levels;
         c.omega = cfg->omega;
         c.smoother = cfg->smoother;
+        FAMG_REQUIRE(cfg->chebyshev_steps >= 0, AMG_ERR_INVALID, "sa config: negative chebyshev_steps");
+        c.chebyshev_steps = cfg->chebyshev_steps;
         *mg_out = new amg_linop{sa_build(a, near_null, ld, k, weights, c, nullptr)};
     });
 }

@@ -69,7 +69,7 @@ P = C.POINTER
 
 AMG_MEM_HOST, AMG_MEM_DEVICE = 0, 1
 KINDS = {0: "csr", 1: "diag", 2: "sgs", 3: "coarse", 4: "multigrid", 5: "dist_csr",
-         6: "dist_multigrid", 7: "composite", 8: "block"}
+         6: "dist_multigrid", 7: "composite", 8: "block", 9: "chebyshev"}
 
 # name -> (restype, argtypes); every exported symbol of include/amg.h
 SIGNATURES = {
@@ -212,6 +212,9 @@ SIGNATURES = {
     "amg_adaptive_build": (i32, [vp, vp, i64, i64, vp, vp, P(vp)]),
     "amg_pcg_solve_block": (i32, [vp, vp, vp, i64, vp, i64, i64, i64, dbl, dbl, vp, i64, vp]),
     "amg_stationary_solve_block": (i32, [vp, vp, vp, i64, vp, i64, i64, i64, dbl, vp, i64, vp]),
+    "amg_chebyshev_config_default": (i32, [vp]),
+    "amg_chebyshev_create": (i32, [vp, vp, P(vp)]),
+    "amg_chebyshev_info": (i32, [vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -648,6 +651,36 @@ def sgs_fused(S):
     return bool(v.value)
 
 
+class ChebyshevConfig(C.Structure):
+    """amg_chebyshev_config (include/amg.h)."""
+    _fields_ = [("steps", i64), ("eig_iters", i64), ("eig_ratio", dbl), ("boost", dbl), ("lambda_max", dbl)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _ck(_lib.amg_chebyshev_config_default(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def new_chebyshev(A, steps=2, eig_ratio=20.0, eig_iters=10, boost=1.1, lambda_max=0.0):
+    """Chebyshev polynomial smoother on D^-1 A over [lambda_max / eig_ratio, lambda_max]
+    (amg_chebyshev_create): lambda_max = min(boost * Lanczos Ritz value, row-sum bound),
+    or the caller's when lambda_max > 0."""
+    cfg = ChebyshevConfig(steps=steps, eig_ratio=eig_ratio, eig_iters=eig_iters, boost=boost, lambda_max=lambda_max)
+    h = vp()
+    _ck(_lib.amg_chebyshev_create(A.h, C.byref(cfg), C.byref(h)))
+    return _wrap(h, A.ctx)
+
+
+def chebyshev_info(S):
+    """{'lambda_max', 'lambda_min', 'steps', 'ritz' (0.0: Lanczos not run), 'row_sum_bound'
+    (0.0: not computed), 'eig_iters' (Lanczos steps run)} of a Chebyshev smoother."""
+    info = np.zeros(6, np.float64)
+    _ck(_lib.amg_chebyshev_info(S.h, info.ctypes.data_as(vp)))
+    return {"lambda_max": float(info[0]), "lambda_min": float(info[1]), "steps": int(info[2]),
+            "ritz": float(info[3]), "row_sum_bound": float(info[4]), "eig_iters": int(info[5])}
+
+
 def CoarseCholesky(A):
     """CoarseSolverKind::Cholesky.build_from_sparse (coarse_solvers.rs:22-33)."""
     h = vp()
@@ -825,15 +858,20 @@ def nn_stationary_l1(A, x, iters=3):
     return x
 
 
-SMOOTHERS = {"jacobi": 0, "l1": 1, "sgs": 2, "block": 3}
+SMOOTHERS = {"jacobi": 0, "l1": 1, "sgs": 2, "block": 3, "chebyshev": 4}
+
+
+def _smoother_code(smoother):
+    return SMOOTHERS[smoother] if isinstance(smoother, str) else int(smoother)
 
 
 def sa_build_box(A, dims, box=(2, 2, 2), coarsest_dim=1000, max_levels=0, omega=0.66,
                  smoother="jacobi"):
-    """SA hierarchy + multigrid on a structured grid (Hierarchy::coarsen + Multigrid)."""
+    """SA hierarchy + multigrid on a structured grid (Hierarchy::coarsen + Multigrid).
+    smoother: a name of SMOOTHERS or its code (4 / 'chebyshev': the default config)."""
     h = vp()
     _ck(_lib.amg_sa_build_box(A.h, dims[0], dims[1], dims[2], box[0], box[1], box[2],
-                              coarsest_dim, max_levels, omega, SMOOTHERS[smoother], C.byref(h)))
+                              coarsest_dim, max_levels, omega, _smoother_code(smoother), C.byref(h)))
     return Multigrid._from_handle(h, A.ctx)
 
 
@@ -842,7 +880,7 @@ class SaConfig(C.Structure):
     (interpolation/mod.rs:62-79, hierarchy.rs:21-36)."""
     _fields_ = [("block_size", i64), ("candidate_dimension", i64), ("strength_depth", i64),
                 ("smoothing_steps", i64), ("coarsest_dim", i64), ("max_levels", i64),
-                ("omega", dbl), ("smoother", i32), ("reserved", i32)]
+                ("omega", dbl), ("smoother", i32), ("chebyshev_steps", i32)]
 
     def __init__(self, **kw):
         super().__init__()
@@ -868,7 +906,8 @@ def smoothed_aggregation(A, near_null, weights=None, **config):
     AggregationConfig, hierarchy.rs:190-248; interpolation/mod.rs:730-836).
     near_null: n x k candidates; weights: k strength weights (None: 1/v^T A v);
     config: SaConfig fields (block_size, candidate_dimension, strength_depth,
-    smoothing_steps, coarsest_dim, max_levels, omega, smoother)."""
+    smoothing_steps, coarsest_dim, max_levels, omega, smoother -- a name of SMOOTHERS
+    or its code -- and chebyshev_steps for smoother 4 / 'chebyshev')."""
     cfg = SaConfig(**config)
     nn = _colmajor_host(near_null, A.nrows)
     w = None if weights is None else np.ascontiguousarray(weights, np.float64)
@@ -1044,7 +1083,7 @@ class AdaptiveConfig(C.Structure):
     def __init__(self, **kw):
         super().__init__()
         _ck(_lib.amg_adaptive_config_default(C.byref(self)))
-        sa_fields = {name for name, _ in SaConfig._fields_} - {"reserved"}
+        sa_fields = {name for name, _ in SaConfig._fields_}
         for k, v in kw.items():
             if k in ("max_components", "test_iters"):
                 setattr(self, k, v)

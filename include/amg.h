@@ -53,7 +53,8 @@ typedef enum amg_linop_kind {
     AMG_KIND_DIST_CSR = 5,  /* row-block distributed sparse matrix */
     AMG_KIND_DIST_MULTIGRID = 6,
     AMG_KIND_COMPOSITE = 7, /* Composite (preconditioners/composite.rs) */
-    AMG_KIND_BLOCK = 8      /* BlockSmoother (preconditioners/block_smoothers.rs) */
+    AMG_KIND_BLOCK = 8,     /* BlockSmoother (preconditioners/block_smoothers.rs) */
+    AMG_KIND_CHEBYSHEV = 9  /* Chebyshev polynomial smoother (no reference counterpart) */
 } amg_linop_kind;
 
 typedef struct amg_ctx amg_ctx;
@@ -277,7 +278,8 @@ amg_status amg_linop_dims(const amg_linop *op, int64_t *nrows, int64_t *ncols);
 /* LinOp::apply: out = M * rhs, out overwritten (par_spmm.rs:117,151; multigrid.rs:469).
  * out: nrows x k (ld_out), rhs: ncols x k (ld_rhs).  k > 1: a CSR matrix runs one
  * SpMM; a multigrid or a Composite runs one block cycle (flag 11; chunks of 32
- * columns), each column bitwise the k = 1 result; AMG_MEM_HOST blocks are staged
+ * columns), a Chebyshev smoother its k-wide vector kernels with A read once per 8
+ * columns, each column bitwise the k = 1 result; AMG_MEM_HOST blocks are staged
  * whole.  Other kinds apply column by column. */
 amg_status amg_linop_apply(amg_linop *op, double *out, int64_t ld_out, const double *rhs,
                            int64_t ld_rhs, int64_t k, amg_mem mem);
@@ -322,6 +324,47 @@ amg_status amg_sgs_ncolors(const amg_linop *op, int64_t *ncolors);
 /* Storage of the color sweeps: info4 = {colors, kernel (as amg_csr_spmv_info:
  * 1 SELL, 3 DIA codes of the color-permuted copy, ...), diagonals, code bits}. */
 amg_status amg_sgs_info(const amg_linop *op, int64_t *info4);
+/* Chebyshev polynomial smoother (no reference counterpart -- like SGS a new
+ * definition).  With D = diag(A), lambda_max an upper bound on the
+ * spectrum of D^-1 A and lambda_min = lambda_max / eig_ratio:
+ *   theta = (lambda_max + lambda_min) / 2, delta = (lambda_max - lambda_min) / 2,
+ *   sigma = theta / delta, rho_0 = 1 / sigma, c2_0 = 1 / theta,
+ *   rho_k = 1 / (2 sigma - rho_{k-1}), c1_k = rho_k rho_{k-1}, c2_k = 2 rho_k / delta
+ * (host, fp64, these expressions in this order), and z = S b from z = 0 is
+ *   d = c2_0 (dinv b), x = d, r = b;
+ *   k = 1 .. steps-1:  r = r - A d;  d = c1_k d + c2_k (dinv r);  x = x + d
+ * element-wise without contraction: steps - 1 products with A (the RESID SpMV)
+ * and one fused vector pass per term.  S is symmetric (PCG stays valid), needs
+ * no colouring, and is k-wide: amg_linop_apply with k > 1 runs the same vector
+ * kernels over grid (rows, columns) and reads A once per 8 columns, every column
+ * bitwise the k = 1 result; inside a multigrid the block V-cycle (flag 11) has
+ * nothing per column left on a Chebyshev level.  Single-GPU: the distributed
+ * multigrid takes diagonal and SGS smoothers only and refuses this one
+ * (amg_dist_multigrid_create, AMG_ERR_UNSUPPORTED).
+ * The bound, at creation, on the device: G = max_i sum_j |a_ij| / a_ii (always
+ * >= lambda_max(D^-1 A)) and rho_L, the largest Ritz value of eig_iters Lanczos
+ * steps on D^-1 A in the D inner product from the start vector
+ * q_i = ((i * 2654435761) mod 2^32) / 2^32 - 0.5 (the ABI carries no RNG; the
+ * <= 64 x 64 tridiagonal eigenproblem is solved on the host);
+ * lambda_max = min(boost * rho_L, G); eig_iters = 0: G alone; cfg.lambda_max > 0:
+ * that value, nothing estimated (info reports rho_L = G = 0).
+ * AMG_ERR_INVALID: null handle or out, steps < 1, eig_iters outside 0..64,
+ * eig_ratio <= 1, boost < 1, lambda_max < 0 (checked before a device is
+ * touched); AMG_ERR_DIM: A not square; AMG_ERR_NOT_SPD: a diagonal entry <= 0
+ * or missing. */
+typedef struct amg_chebyshev_config {
+    int64_t steps;      /* m >= 1 (default 2) */
+    int64_t eig_iters;  /* Lanczos steps, 0..64; 0 = the row-sum bound G (default 10) */
+    double eig_ratio;   /* > 1 (default 20) */
+    double boost;       /* >= 1 (default 1.1) */
+    double lambda_max;  /* > 0: use this bound, estimate nothing (default 0) */
+} amg_chebyshev_config;
+amg_status amg_chebyshev_config_default(amg_chebyshev_config *cfg);
+/* cfg NULL = the defaults. */
+amg_status amg_chebyshev_create(const amg_linop *A, const amg_chebyshev_config *cfg, amg_linop **out);
+/* info6 = {lambda_max, lambda_min, steps, lanczos_ritz (0 if not run), row_sum_bound G
+ * (0 if not computed), eig_iters run}; AMG_ERR_INVALID on another kind. */
+amg_status amg_chebyshev_info(const amg_linop *op, double *info6);
 /* CoarseSolverKind::Cholesky (coarse_solvers.rs:21-33, SparseCholeskySolve
  * :172-181): exact coarse solve.  Returns AMG_ERR_NOT_SPD if A is not SPD and
  * AMG_ERR_UNSUPPORTED above 16384 rows (dense factor). */
@@ -468,8 +511,9 @@ amg_status amg_nn_stationary_l1(const amg_linop *A, int64_t iters, double *x);
  * box aggregates standing in for the modularity partitioner -- DESIGN.md).
  * Coarsens until the coarse size <= coarsest_dim or max_levels (0 = unlimited).
  * smoother: 0 Jacobi(omega), 1 L1, 2 SGS (greedy coloring; L1 on levels needing
- * > 32 colors), 3 BlockSmoother over the level's box aggregates, on every level
- * but the coarsest, which gets the Cholesky coarse solve.  Returns the multigrid. */
+ * > 32 colors), 3 BlockSmoother over the level's box aggregates, 4 Chebyshev
+ * (amg_chebyshev_create with the default config), on every level but the
+ * coarsest, which gets the Cholesky coarse solve.  Returns the multigrid. */
 amg_status amg_sa_build_box(amg_linop *A, int64_t nx, int64_t ny, int64_t nz, int64_t bx,
                             int64_t by, int64_t bz, int64_t coarsest_dim, int64_t max_levels,
                             double omega, int32_t smoother, amg_linop **mg_out);
@@ -490,8 +534,9 @@ typedef struct amg_sa_config {
     int64_t coarsest_dim;        /* stop when the coarse size <= this (default 1000) */
     int64_t max_levels;          /* 0 = unlimited */
     double omega;                /* Jacobi smoother weight (smoother 0) */
-    int32_t smoother;            /* 0 Jacobi, 1 L1 (default), 2 SGS, 3 BlockSmoother(aggregates) */
-    int32_t reserved;
+    int32_t smoother;            /* 0 Jacobi, 1 L1 (default), 2 SGS, 3 BlockSmoother(aggregates), 4 Chebyshev */
+    int32_t chebyshev_steps;     /* smoother 4: steps per application, 0 = the default (2); the former
+                                    `reserved` field, same layout */
 } amg_sa_config;
 amg_status amg_sa_config_default(amg_sa_config *cfg);
 /* near_null: n x k column-major (leading dimension ld), host; weights: k host
@@ -704,7 +749,8 @@ amg_status amg_comm_allreduce_sum(amg_comm *comm, double *value);
  * [s[l*(nranks+1)+p], s[l*(nranks+1)+p+1])).  Levels from the first one with
  * fewer than agglomerate_rows rows down are run redundantly on every rank.
  * Every distributed level must be smoothed by a diagonal (Jacobi/L1/L2) or a
- * multicolor SGS smoother; SGS sweeps the global coloring restricted to the
+ * multicolor SGS smoother (a Chebyshev level is refused: AMG_ERR_UNSUPPORTED);
+ * SGS sweeps the global coloring restricted to the
  * owned rows with one halo exchange before every color (the single-GPU sweep's
  * values on every rank).  apply() maps the rank's owned rows of rhs (n_own) to
  * its owned rows of out.  k > 1 columns run column by column: the distributed

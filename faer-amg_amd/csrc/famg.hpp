@@ -501,6 +501,32 @@ void cg_xpay_cols(double *P, int64_t ldp, const double *Z, int64_t ldz, const do
 void cg_add_cols(double *X, int64_t ldx, const int32_t *map, const double *Z, int64_t ldz, int64_t n, int64_t k,
                  hipStream_t s);
 
+// G (kp2 entries, a multiple of 256) = nblk partial arrays of kp2 entries summed in a
+// fixed order (nearnull.hip k_gram_final: the second launch of a Gram product)
+void gram_final(const double *partials, int64_t nblk, int kp2, double *G, hipStream_t s);
+
+// tall-skinny kernels of the coupled block CG (bcg.hip): column-major device blocks
+constexpr int64_t BCG_MAX_W = 32;  // widest block: the k x k coupling cannot be chunked
+// device scratch of the Gram products of one call
+struct BcgWork {
+    DevBuf<double> partials, G;
+    int64_t gram_blocks = 0, rows_per_block = 0;
+    void reserve(const Ctx &ctx, int64_t n);
+};
+// hC (host; pinned for a copy that overlaps) = X^T [Y1 | Y2], w x (m1 + m2) in a
+// row-major array of row stride 16 ceil((m1 + m2) / 16) (returned), 16 ceil(w / 16)
+// rows, zero past the operands; 1 <= w, m1 <= 32, 0 <= m2 <= 32 (m2 = 0: Y2 unread).
+// Two launches and an asynchronous copy: the caller synchronises before reading hC.
+int bcg_gram(const double *X, int64_t ldx, int64_t w, const double *Y1, int64_t ld1, int64_t m1, const double *Y2,
+             int64_t ld2, int64_t m2, int64_t n, BcgWork &ws, double *hC, hipStream_t s);
+// C (w x m column-major) into bcg_gemm's layout: column stride 8 ceil(w / 8), zero filled
+void bcg_pack_coef(const double *C, int64_t w, int64_t m, double *packed);
+// OUT = Y + sign * X Cd (X n x w, w <= 32; Cd on the device, packed; sign +1 or -1).
+// OUT may be Y or X (every lane reads its row of X before it writes).  name: the
+// launch-log entry ("bcg_update", "bcg_dir"); byte model 8 n (2 m + w).
+void bcg_gemm(const char *name, double *OUT, int64_t ldo, const double *Y, int64_t ldy, const double *X, int64_t ldx,
+              const double *Cd, int64_t w, int64_t m, int64_t n, int sign, hipStream_t s);
+
 // marker kernel for rocprofv3 traces (amg_trace_mark)
 void trace_mark(Ctx &ctx, int32_t tag);
 

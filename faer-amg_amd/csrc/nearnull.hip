@@ -124,6 +124,10 @@ __global__ __launch_bounds__(256) void k_gram_final(const double *__restrict__ p
     }
 }
 
+void gram_final(const double *partials, int64_t nblk, int kp2, double *G, hipStream_t s) {
+    k_gram_final<<<dim3((unsigned)(kp2 / 16)), dim3(256), 0, s>>>(partials, nblk, kp2, G);
+}
+
 // ------------------------------------------------------------------ update
 
 // X <- X Rinv in place: one row per lane in registers, Rinv (KB x KB column-major, upper
@@ -235,8 +239,7 @@ static void gram(const double *X, int64_t ld, int64_t n, int64_t k, NearNullWork
     case 3: k_gram_partial<3><<<grid, block, 0, s>>>(X, ld, n, (int)k, w.rows_per_block, w.partials.get()); break;
     default: k_gram_partial<4><<<grid, block, 0, s>>>(X, ld, n, (int)k, w.rows_per_block, w.partials.get()); break;
     }
-    k_gram_final<<<dim3((unsigned)(kp * kp / 16)), block, 0, s>>>(w.partials.get(), w.gram_blocks, kp * kp,
-                                                                          w.G.get());
+    gram_final(w.partials.get(), w.gram_blocks, kp * kp, w.G.get(), s);
     FAMG_CHECK_HIP(hipGetLastError());
     FAMG_CHECK_HIP(hipMemcpyAsync(w.hG.data(), w.G.get(), (size_t)kp * kp * sizeof(double), hipMemcpyDeviceToHost, s));
     FAMG_CHECK_HIP(hipStreamSynchronize(s));

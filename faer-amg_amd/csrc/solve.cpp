@@ -316,6 +316,154 @@ void stationary_block_impl(LinOp &A, LinOp &M, const double *B, int64_t ldb, dou
     }
 }
 
+// ------------------------------------------------------- coupled block CG
+
+void RankChol::factor(const double *G, int64_t ldg, int64_t k, double rank_tol) {
+    sc.assign(k, 0.0);
+    cand.clear();
+    order.clear();
+    for (int64_t j = 0; j < k; j++) {
+        const double g = G[j * ldg + j];
+        if (g > 0.0) {  // a zero or converged direction, a non-SPD A or M, a NaN: dropped
+            cand.push_back(j);
+            sc[j] = 1.0 / std::sqrt(g);
+        }
+    }
+    nc = (int64_t)cand.size();
+    C.assign(nc * nc, 0.0);
+    L.assign(nc * nc, 0.0);
+    std::vector<double> dg(nc, 1.0);
+    std::vector<char> taken(nc, 0);
+    for (int64_t a = 0; a < nc; a++)
+        for (int64_t b = 0; b < nc; b++) {
+            const int64_t i = cand[a], j = cand[b];
+            C[a * nc + b] = a == b ? 1.0 : ((0.5 * (G[i * ldg + j] + G[j * ldg + i])) * sc[i]) * sc[j];
+        }
+    for (int64_t t = 0; t < nc; t++) {
+        int64_t p = -1;
+        for (int64_t a = 0; a < nc; a++)
+            if (!taken[a] && (p < 0 || dg[a] > dg[p])) p = a;  // ties: the lower index
+        if (p < 0 || !(dg[p] > rank_tol)) break;
+        const double lpp = std::sqrt(dg[p]);
+        L[p * nc + t] = lpp;
+        taken[p] = 1;
+        order.push_back(p);
+        for (int64_t a = 0; a < nc; a++) {
+            if (taken[a]) continue;
+            double s = C[a * nc + p];
+            for (int64_t u = 0; u < t; u++) s -= L[a * nc + u] * L[p * nc + u];
+            const double l = s / lpp;
+            L[a * nc + t] = l;
+            dg[a] -= l * l;
+        }
+    }
+}
+
+void RankChol::solve(const double *Y, int64_t ldy, int64_t k, int64_t m, double *out) const {
+    const int64_t r = rank();
+    std::vector<double> z(std::max<int64_t>(1, r));
+    std::fill(out, out + k * m, 0.0);
+    for (int64_t j = 0; j < m; j++) {
+        for (int64_t t = 0; t < r; t++) {
+            const int64_t a = order[t];
+            double s = sc[cand[a]] * Y[cand[a] * ldy + j];
+            for (int64_t u = 0; u < t; u++) s -= L[a * nc + u] * z[u];
+            z[t] = s / L[a * nc + t];
+        }
+        for (int64_t t = r; t-- > 0;) {
+            double s = z[t];
+            for (int64_t u = t + 1; u < r; u++) s -= L[order[u] * nc + t] * z[u];
+            z[t] = s / L[order[t] * nc + t];
+        }
+        for (int64_t t = 0; t < r; t++) out[j * k + cand[order[t]]] = sc[cand[order[t]]] * z[t];
+    }
+}
+
+void block_cg_impl(LinOp &A, LinOp *M, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k,
+                   int64_t max_iter, double rel_tol, double abs_tol, double rank_tol, double *hist, int64_t ld_hist,
+                   int64_t *ranks, int64_t *iters) {
+    if (k <= 0) return;
+    FAMG_REQUIRE(k <= BCG_MAX_W, AMG_ERR_UNSUPPORTED, "block CG: more than 32 columns");
+    if (!(rank_tol > 0.0)) rank_tol = 0x1p-26;
+    hipStream_t s = A.ctx->stream;
+    const int64_t n = A.nrows, ld = std::max<int64_t>(1, n);
+    DevBuf<double> blocks((size_t)4 * ld * k), scal((size_t)k * (VEC_DOT_PARTIALS + 2)), coef(2 * BCG_MAX_W * BCG_MAX_W);
+    PinnedBuf<double> h_res(2 * (size_t)k), h_gram(2 * BCG_MAX_W * BCG_MAX_W), h_coef(2 * BCG_MAX_W * BCG_MAX_W);
+    BcgWork gw;
+    gw.reserve(*A.ctx, n);
+    double *R = blocks.get(), *Z = R + ld * k, *P = Z + ld * k, *Q = P + ld * k;
+    double *Zp = M ? Z : R;  // identity preconditioner: z is r itself
+    double *partials = scal.get(), *res = partials + k * VEC_DOT_PARTIALS;
+    double *d_alpha = coef.get(), *d_beta = d_alpha + BCG_MAX_W * BCG_MAX_W;
+    double *h_alpha = h_coef.p, *h_beta = h_alpha + BCG_MAX_W * BCG_MAX_W;
+    const size_t coef_bytes = (size_t)k * 8 * ceil_div(k, 8) * sizeof(double);
+    auto *a = dynamic_cast<CsrOp *>(&A);
+    std::vector<double> bn(k), tol(k), sol(k * k);
+    RankChol ch;
+    // the squared column norms of V into res[off ..], no synchronise
+    auto norms = [&](const double *V, int64_t ldv, int64_t off) {
+        cg_dot_cols(V, ldv, V, ldv, n, k, partials, s);
+        cg_final_cols(CG_FINAL_STORE, partials, res + off, nullptr, k, s);
+    };
+    auto fetch = [&](int64_t cnt) {
+        FAMG_CHECK_HIP(hipMemcpyAsync(h_res.p, res, cnt * sizeof(double), hipMemcpyDeviceToHost, s));
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+    };
+    residual_block(A, a, R, ld, B, ldb, X, ldx, k);
+    norms(B, ldb, 0);
+    norms(R, ld, k);
+    fetch(2 * k);
+    bool done = true;
+    for (int64_t c = 0; c < k; c++) {
+        bn[c] = std::sqrt(h_res.p[c]);
+        tol[c] = std::max(abs_tol, rel_tol * bn[c]);
+        done = done && std::sqrt(h_res.p[k + c]) <= tol[c];
+    }
+    if (done) {
+        *iters = 0;
+        return;
+    }
+    if (M) M->apply_block(Z, ld, R, ld, k);
+    vec_copy_cols(P, ld, Zp, ld, n, k, s);
+    for (int64_t it = 1; it <= max_iter; it++) {
+        if (a) spmm_epi(a->m, P, ld, Q, ld, k, SPMV_SET, SpmmEpi{}, s);
+        else A.apply_block(Q, ld, P, ld, k);
+        // [G | S] = P^T [Q | R]: synchronisation 1
+        const int ldg = bcg_gram(P, ld, k, Q, ld, k, R, ld, k, n, gw, h_gram.p, s);
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+        ch.factor(h_gram.p, ldg, k, rank_tol);
+        ch.solve(h_gram.p + k, ldg, k, k, sol.data());
+        if (ranks) ranks[it - 1] = ch.rank();
+        bcg_pack_coef(sol.data(), k, k, h_alpha);
+        FAMG_CHECK_HIP(hipMemcpyAsync(d_alpha, h_alpha, coef_bytes, hipMemcpyHostToDevice, s));
+        bcg_gemm("bcg_update", X, ldx, X, ldx, P, ld, d_alpha, k, k, n, +1, s);
+        bcg_gemm("bcg_update", R, ld, R, ld, Q, ld, d_alpha, k, k, n, -1, s);
+        norms(R, ld, 0);
+        fetch(k);  // synchronisation 2
+        done = true;
+        for (int64_t c = 0; c < k; c++) {
+            const double rn = std::sqrt(h_res.p[c]);
+            if (hist) hist[c * ld_hist + it - 1] = bn[c] == 0.0 ? rn : rn / bn[c];
+            done = done && rn <= tol[c];
+        }
+        if (done) {
+            *iters = it;
+            return;
+        }
+        if (ch.rank() == 0 || it == max_iter) break;  // no direction left; the last z, beta and p are never read
+        if (M) M->apply_block(Z, ld, R, ld, k);
+        // T = Q^T Z: synchronisation 3 (the factor of G serves beta too)
+        const int ldt = bcg_gram(Q, ld, k, Zp, ld, k, nullptr, 0, 0, n, gw, h_gram.p, s);
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+        ch.solve(h_gram.p, ldt, k, k, sol.data());
+        bcg_pack_coef(sol.data(), k, k, h_beta);
+        FAMG_CHECK_HIP(hipMemcpyAsync(d_beta, h_beta, coef_bytes, hipMemcpyHostToDevice, s));
+        bcg_gemm("bcg_dir", P, ld, Zp, ld, P, ld, d_beta, k, k, n, -1, s);
+    }
+    *iters = max_iter + 1;
+    FAMG_CHECK_HIP(hipStreamSynchronize(s));
+}
+
 void CompositeOp::apply(double *out, const double *rhs) {
     std::lock_guard<std::mutex> lk(mtx);
     hipStream_t s = ctx->stream;
@@ -513,6 +661,77 @@ amg_status amg_stationary_solve_block(amg_linop *A, amg_linop *M, const double *
         if (k == 0) return;
         a.ctx->set_device();
         stationary_block_impl(a, m, B, ldb, X, ldx, k, max_iter, rel_tol, hist, ld_hist, iters);
+    });
+}
+
+amg_status amg_block_cg_solve(amg_linop *A, amg_linop *M, const double *B, int64_t ldb, double *X, int64_t ldx,
+                              int64_t k, int64_t max_iter, double rel_tol, double abs_tol, double rank_tol,
+                              double *hist, int64_t ld_hist, int64_t *ranks, int64_t *iters) {
+    return guard([&] {
+        FAMG_REQUIRE(B && X && iters, AMG_ERR_INVALID, "block CG: null B, X or iters");
+        FAMG_REQUIRE(k >= 0, AMG_ERR_INVALID, "block CG: negative column count");
+        FAMG_REQUIRE(k <= BCG_MAX_W, AMG_ERR_UNSUPPORTED,
+                     "block CG: more than 32 columns (the k x k coupling cannot be chunked)");
+        FAMG_REQUIRE(max_iter >= 0, AMG_ERR_INVALID, "block CG: negative max_iter");
+        FAMG_REQUIRE(!hist || ld_hist >= max_iter, AMG_ERR_INVALID, "block CG: ld_hist below max_iter");
+        FAMG_REQUIRE(rank_tol < 1.0, AMG_ERR_INVALID, "block CG: rank_tol must be below 1 (<= 0: the default 2^-26)");
+        FAMG_REQUIRE(B != X, AMG_ERR_INVALID, "block CG: B must not alias X");
+        LinOp &a = need_op(A);
+        LinOp *m = M ? &need_op(M) : nullptr;
+        block_solve_ops(a, m, B, ldb, X, ldx, k);
+        if (k == 0) return;
+        a.ctx->set_device();
+        block_cg_impl(a, m, B, ldb, X, ldx, k, max_iter, rel_tol, abs_tol, rank_tol, hist, ld_hist, ranks, iters);
+    });
+}
+
+amg_status amg_block_gram(amg_ctx *ctx, const double *X, int64_t ldx, int64_t w, const double *Y1, int64_t ld1,
+                          int64_t m1, const double *Y2, int64_t ld2, int64_t m2, int64_t n, double *C) {
+    return guard([&] {
+        FAMG_REQUIRE(X && Y1 && C, AMG_ERR_INVALID, "block gram: null X, Y1 or C");
+        FAMG_REQUIRE(w >= 1 && m1 >= 1 && m2 >= 0 && n >= 0, AMG_ERR_INVALID,
+                     "block gram: need w >= 1, m1 >= 1, m2 >= 0 and n >= 0");
+        FAMG_REQUIRE(w <= BCG_MAX_W && m1 <= BCG_MAX_W && m2 <= BCG_MAX_W, AMG_ERR_UNSUPPORTED,
+                     "block gram: more than 32 columns in a block");
+        FAMG_REQUIRE(m2 == 0 || Y2, AMG_ERR_INVALID, "block gram: null Y2 with m2 > 0");
+        FAMG_REQUIRE(ldx >= n && ld1 >= n && (m2 == 0 || ld2 >= n), AMG_ERR_INVALID,
+                     "block gram: leading dimension too small");
+        FAMG_REQUIRE(ctx, AMG_ERR_INVALID, "null context");
+        ctx->ctx.set_device();
+        hipStream_t s = ctx->ctx.stream;
+        BcgWork gw;
+        gw.reserve(ctx->ctx, n);
+        PinnedBuf<double> h(2 * BCG_MAX_W * BCG_MAX_W);
+        const int ldc = bcg_gram(X, ldx, w, Y1, ld1, m1, m2 ? Y2 : nullptr, ld2, m2, n, gw, h.p, s);
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+        for (int64_t j = 0; j < m1 + m2; j++)
+            for (int64_t i = 0; i < w; i++) C[j * w + i] = h.p[i * ldc + j];
+    });
+}
+
+amg_status amg_block_gemm_update(amg_ctx *ctx, double *Y, int64_t ldy, const double *X, int64_t ldx, const double *C,
+                                 int64_t w, int64_t m, int64_t n, int32_t sign) {
+    return guard([&] {
+        FAMG_REQUIRE(X && Y && C, AMG_ERR_INVALID, "block gemm update: null Y, X or C");
+        FAMG_REQUIRE(w >= 1 && m >= 1 && n >= 0, AMG_ERR_INVALID, "block gemm update: need w >= 1, m >= 1 and n >= 0");
+        FAMG_REQUIRE(w <= BCG_MAX_W && m <= BCG_MAX_W, AMG_ERR_UNSUPPORTED,
+                     "block gemm update: more than 32 columns in a block");
+        FAMG_REQUIRE(sign == 1 || sign == -1, AMG_ERR_INVALID, "block gemm update: sign must be +1 or -1");
+        FAMG_REQUIRE(ldx >= n && ldy >= n, AMG_ERR_INVALID, "block gemm update: leading dimension too small");
+        if (n > 0) {  // the two blocks' extents must not overlap
+            const double *xe = X + (w - 1) * ldx + n, *ye = Y + (m - 1) * ldy + n;
+            FAMG_REQUIRE(xe <= Y || ye <= X, AMG_ERR_INVALID, "block gemm update: X must not alias Y");
+        }
+        FAMG_REQUIRE(ctx, AMG_ERR_INVALID, "null context");
+        ctx->ctx.set_device();
+        hipStream_t s = ctx->ctx.stream;
+        DevBuf<double> cd(BCG_MAX_W * BCG_MAX_W);
+        PinnedBuf<double> h(BCG_MAX_W * BCG_MAX_W);
+        bcg_pack_coef(C, w, m, h.p);
+        FAMG_CHECK_HIP(hipMemcpyAsync(cd.get(), h.p, (size_t)m * 8 * ceil_div(w, 8) * sizeof(double),
+                                      hipMemcpyHostToDevice, s));
+        bcg_gemm("bcg_update", Y, ldy, Y, ldy, X, ldx, cd.get(), w, m, n, sign, s);
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
     });
 }
 

@@ -53,6 +53,36 @@ void pcg_block_impl(LinOp &A, LinOp *M, const double *B, int64_t ldb, double *X,
 void stationary_block_impl(LinOp &A, LinOp &M, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k,
                            int64_t max_iter, double rel_tol, double *hist, int64_t ld_hist, int64_t *iters);
 
+// The rank-revealing solve G^+ Y of the coupled block CG (host, fp64; amg.h and
+// DESIGN.md 15): G symmetrised, columns with g_jj <= 0 dropped, the rest scaled
+// to unit diagonal, Cholesky with diagonal pivoting (largest remaining diagonal
+// first, ties to the lower index) stopped at the first pivot <= rank_tol.
+// G and Y are read as element (i, j) at [i * ld + j]; solve() writes a k x m
+// column-major result whose rows of dropped columns are zero.
+struct RankChol {
+    int64_t nc = 0;                   // columns with a positive diagonal
+    std::vector<int64_t> cand, order; // their indices; the pivots taken, as positions in cand
+    std::vector<double> sc, C, L;     // D^-1/2; the scaled matrix and its factor (nc x nc, row a = candidate a)
+    int64_t rank() const { return (int64_t)order.size(); }
+    void factor(const double *G, int64_t ldg, int64_t k, double rank_tol);
+    void solve(const double *Y, int64_t ldy, int64_t k, int64_t m, double *out) const;
+};
+
+// Coupled block CG over k <= 32 right-hand sides (single GPU; the counterpart of
+// faer's conjugate_gradient on an n x k rhs, defined in amg.h / DESIGN.md 15): one
+// k x k system for the step and one for the new directions per iteration, all
+// columns searched in the sum of their Krylov spaces.  The workspace R, Z, P, Q
+// is n x k (leading dimension n), allocated once per call.  Q = A P and B - A X
+// run as one SpMM when A is a CSR matrix, M through apply_block; the Gram products
+// and the updates are bcg.hip's kernels, the norms cg_dot_cols after the update.
+// At most three host synchronisations per iteration for all columns together --
+// (G, S) down and alpha up, the norms, T down and beta up (amg_pcg_solve: three
+// per column).  hist: max_iter x k column-major or null; ranks: max_iter entries
+// or null; *iters: one count for the block.
+void block_cg_impl(LinOp &A, LinOp *M, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k,
+                   int64_t max_iter, double rel_tol, double abs_tol, double rank_tol, double *hist, int64_t ld_hist,
+                   int64_t *ranks, int64_t *iters);
+
 // Composite (preconditioners/composite.rs:11-83): components c_0..c_{m-1}
 // applied c_{m-1}, ..., c_1, c_0, c_1, ..., c_{m-1}; each step
 // out += c(r); r = rhs - A out, starting from out = 0, r = rhs.

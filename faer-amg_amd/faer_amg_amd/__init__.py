@@ -215,6 +215,9 @@ SIGNATURES = {
     "amg_chebyshev_config_default": (i32, [vp]),
     "amg_chebyshev_create": (i32, [vp, vp, P(vp)]),
     "amg_chebyshev_info": (i32, [vp, vp]),
+    "amg_block_cg_solve": (i32, [vp, vp, vp, i64, vp, i64, i64, i64, dbl, dbl, dbl, vp, i64, vp, P(i64)]),
+    "amg_block_gram": (i32, [vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, vp]),
+    "amg_block_gemm_update": (i32, [vp, vp, i64, vp, i64, vp, i64, i64, i64, i32]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -1176,6 +1179,58 @@ def stationary_solve_block(A, M, B, X, max_iter=100, rel_tol=1e-8):
         _ck(_lib.amg_stationary_solve_block(A.h, M.h, pb, ldb, px, ldx, k, max_iter, rel_tol,
                                             hist.ctypes.data_as(vp), ldh, iters.ctypes.data_as(vp)))
     return iters[:k], [hist[:int(iters[c]), c].copy() for c in range(k)]
+
+
+def block_cg_solve(A, M, B, X, max_iter=1000, rel_tol=1e-8, abs_tol=0.0, rank_tol=0.0):
+    """amg_block_cg_solve: the coupled block CG on the k <= 32 columns of B
+    (column-major n x k device tensors, X in/out) -- what faer's conjugate_gradient
+    does with an n x k rhs: one k x k system for the step and one for the new
+    directions per iteration, fewer iterations than the slowest column alone.
+    Returns (iters, hist[:m], ranks[:m]) with m = min(iters, max_iter): one count
+    for the block, hist m x k relative residuals, ranks the directions kept."""
+    pb, ldb, px, ldx, k = _solve_blocks(B, X)
+    ldh = max(max_iter, 1)
+    hist = np.zeros((ldh, max(k, 1)), order="F")
+    ranks = np.zeros(ldh, np.int64)
+    it = i64()
+    with _ordered(A.ctx, AMG_MEM_DEVICE):
+        _ck(_lib.amg_block_cg_solve(A.h, None if M is None else M.h, pb, ldb, px, ldx, k, max_iter, rel_tol, abs_tol,
+                                    rank_tol, hist.ctypes.data_as(vp), ldh, ranks.ctypes.data_as(vp), C.byref(it)))
+    m = min(it.value, max_iter)
+    return it.value, hist[:m, :k].copy(), ranks[:m].copy()
+
+
+def _device_block(X):
+    p, mem, n, k, ld = _dptr(X)
+    if mem != AMG_MEM_DEVICE:
+        raise ValueError("blocks must be device tensors")
+    return p, n, k, ld
+
+
+def block_gram(ctx, X, Y1, Y2=None):
+    """amg_block_gram: X^T [Y1 | Y2] of column-major device blocks (at most 32
+    columns each) as a w x (m1 + m2) numpy array; fp64 matrix cores, fixed order."""
+    px, n, w, ldx = _device_block(X)
+    p1, n1, m1, ld1 = _device_block(Y1)
+    p2, n2, m2, ld2 = _device_block(Y2) if Y2 is not None else (None, n, 0, n)
+    if n1 != n or n2 != n:
+        raise ValueError("the blocks must have equal row counts")
+    out = np.zeros((w, m1 + m2), order="F")
+    with _ordered(ctx, AMG_MEM_DEVICE):
+        _ck(_lib.amg_block_gram(ctx.h, px, ldx, w, p1, ld1, m1, p2, ld2, m2, n, out.ctypes.data_as(vp)))
+    return out
+
+
+def block_gemm_update(ctx, Y, X, Cm, sign=1):
+    """amg_block_gemm_update: Y <- Y + sign * X Cm in place (X n x w, Y n x m
+    column-major device blocks, Cm a host w x m array; sign +1 or -1)."""
+    py, n, m, ldy = _device_block(Y)
+    px, nx, w, ldx = _device_block(X)
+    Cm = np.asfortranarray(Cm, dtype=np.float64)
+    if nx != n or Cm.shape != (w, m):
+        raise ValueError("need X n x w, Cm w x m and Y n x m")
+    with _ordered(ctx, AMG_MEM_DEVICE):
+        _ck(_lib.amg_block_gemm_update(ctx.h, py, ldy, px, ldx, Cm.ctypes.data_as(vp), w, m, n, sign))
 
 
 class BlockSmoother(LinOp):

@@ -677,7 +677,8 @@ amg_status amg_pcg_solve(amg_linop *A, amg_linop *M, const double *b, double *x,
  * X + c*ldx, ...) gives.  This deviates from the reference, whose faer
  * conjugate_gradient couples the columns of an n x k rhs (one k x k system per
  * iteration); independent columns are what keeps each one the single solve, as
- * amg_linop_apply / amg_csr_spmm_epilogue already promise per column.
+ * amg_linop_apply / amg_csr_spmm_epilogue already promise per column
+ * (amg_block_cg_solve below is the coupled form).
  * A P and B - A X run as one SpMM per 8 columns when A is a CSR matrix; M
  * through its block apply (a multigrid or a Composite: one block cycle, flag 11;
  * a Diag: one k-wide scale; other kinds column by column); alpha, beta and r.z
@@ -709,6 +710,79 @@ amg_status amg_stationary_solve_block(amg_linop *A, amg_linop *M, const double *
                                       double *X, int64_t ldx, int64_t k, int64_t max_iter,
                                       double rel_tol, double *hist, int64_t ld_hist,
                                       int64_t *iters);
+
+/* ---- coupled block CG (utils.rs:553-633 with an n x k rhs) ----------------------
+ * What faer's conjugate_gradient does with an n x k right-hand side, which
+ * amg_pcg_solve_block deliberately does not: the columns are coupled, one k x k
+ * system for the step and one for the new directions per iteration, and all k
+ * solutions are searched in the sum of the k Krylov spaces, so the block needs
+ * fewer iterations than its slowest column alone.  faer is not part of the
+ * reference tree; the definition is this one.  Blocks are n x k
+ * column-major device memory, 1 <= k <= 32; small matrices live on the host in
+ * fp64; tol_c = max(abs_tol, rel_tol ||B_c||).
+ *
+ *   R = B - A X;  if every ||R_c|| <= tol_c: iters = 0, return
+ *   Z = M R (M NULL: Z = R);  P = Z
+ *   for it = 1 .. max_iter:
+ *       Q = A P
+ *       G = P^T Q,  S = P^T R                      (k x k each, one pass over P, Q, R)
+ *       alpha = G^+ S;  ranks[it-1] = r            (the rank-revealing solve below)
+ *       X += P alpha;  R -= Q alpha;  ||R_c|| for every c
+ *       hist[it-1, c] = ||R_c|| / ||B_c||          (||B_c|| = 0: ||R_c||)
+ *       if every ||R_c|| <= tol_c: iters = it, return
+ *       if r = 0: break                            (no direction left: not converged)
+ *       Z = M R;  T = Q^T Z;  beta = G^+ T;  P = Z - P beta
+ *   iters = max_iter + 1
+ *
+ * G^+ Y, on the host, the factor of an iteration reused for beta:
+ *   1. G <- (G + G^T) / 2;
+ *   2. a column j with g_jj <= 0 is dropped (a zero or converged direction, a
+ *      non-SPD A or M);
+ *   3. the rest is scaled to unit diagonal, C = D^-1/2 G D^-1/2;
+ *   4. Cholesky of C with diagonal pivoting -- the largest remaining diagonal
+ *      first, ties to the lower index -- stopped at the first pivot <= rank_tol;
+ *   5. the r pivoted columns are kept: G^+ Y solves with their factor, the rows
+ *      of the dropped columns are zero.
+ * rank_tol defaults to 2^-26 = sqrt(eps): a pivot is the squared A-norm distance
+ * of a unit direction from the span of those already taken, and kappa(C) <=
+ * 1/sqrt(eps) keeps alpha, hence the A-conjugacy of the next block, accurate to
+ * about sqrt(eps).  The unit diagonal keeps a right-hand side of norm 1e-9
+ * beside one of norm 1 from being taken for a dependent one.  Dropping a
+ * direction never makes the answer wrong: X and R move by the same alpha, so
+ * R = B - A X holds to rounding whatever r is.
+ *
+ * Q = A P and B - A X run as one SpMM per 8 columns when A is a CSR matrix; M
+ * through its block apply (a multigrid or a Composite: one block cycle; a Diag:
+ * one k-wide scale).  At most three host synchronisations per iteration for all
+ * columns together: (G, S) down and alpha up, the norms, T down and beta up
+ * (amg_pcg_solve: three per column).  Unlike amg_pcg_solve_block, a column is not
+ * bitwise its single solve, and no column is frozen: every X_c keeps moving until
+ * the whole block is within tolerance.  Two calls give equal bits.
+ *
+ * rank_tol <= 0: the default 2^-26; >= 1: AMG_ERR_INVALID.
+ * hist: host, max_iter x k (ld_hist >= max_iter), may be NULL.
+ * ranks: host, max_iter entries, may be NULL.
+ * *iters: one count for the block (0: start within tolerance; max_iter + 1: not converged).
+ * The checks that need no handle come first and touch no device: null B, X or
+ * iters, k < 0, k > 32 (AMG_ERR_UNSUPPORTED), max_iter < 0, hist with ld_hist <
+ * max_iter, rank_tol >= 1 or NaN, B aliasing X.  Then the null handle, a
+ * distributed A or M (AMG_ERR_UNSUPPORTED), AMG_ERR_DIM, the leading dimensions
+ * below n and overlapping extents, as amg_pcg_solve_block.  k = 0 returns AMG_OK
+ * and touches nothing. */
+amg_status amg_block_cg_solve(amg_linop *A, amg_linop *M, const double *B, int64_t ldb, double *X, int64_t ldx,
+                              int64_t k, int64_t max_iter, double rel_tol, double abs_tol, double rank_tol,
+                              double *hist, int64_t ld_hist, int64_t *ranks, int64_t *iters);
+/* The two tall-skinny kernels of the block CG on their own (device blocks, odd
+ * leading dimensions allowed; 1 <= w, m1, m <= 32, 0 <= m2 <= 32, AMG_ERR_UNSUPPORTED
+ * above; both synchronise the context stream).
+ * C (host, w x (m1 + m2) column-major) = X^T [Y1 | Y2]; device blocks; Y2 may be NULL with m2 = 0.
+ * fp64 matrix cores, fixed summation order: two calls give equal bits. */
+amg_status amg_block_gram(amg_ctx *ctx, const double *X, int64_t ldx, int64_t w, const double *Y1, int64_t ld1,
+                          int64_t m1, const double *Y2, int64_t ld2, int64_t m2, int64_t n, double *C);
+/* Y <- Y + sign * X C  (X n x w, C host w x m column-major, Y n x m; sign +1 or -1; X != Y):
+ * per entry an fma chain over X's columns from 0, then one addition or subtraction. */
+amg_status amg_block_gemm_update(amg_ctx *ctx, double *Y, int64_t ldy, const double *X, int64_t ldx,
+                                 const double *C, int64_t w, int64_t m, int64_t n, int32_t sign);
 
 /* ---- multi-GPU (row-block partition + RCCL halo exchange) ------- */
 

@@ -920,7 +920,31 @@ struct StrengthGraph {
 StrengthGraph strength_graph(const CsrOp &A, const double *nn, int64_t ld, int64_t k, const double *w,
                              int64_t depth, int64_t bs);
 // MIS-seeded aggregates of a strength graph; returns the aggregate count
-int64_t aggregate_mis(const StrengthGraph &G, std::vector<int64_t> &agg_of);
+// (stats2, optional: {roots, singleton roots})
+int64_t aggregate_mis(const StrengthGraph &G, std::vector<int64_t> &agg_of, int64_t *stats2 = nullptr);
+// The tail of aggregate_mis, shared with the device path: agg = a label per node
+// (the root's, indexing size0 = the aggregate sizes before any merge), singles =
+// the singleton roots ascending, row q of them = entries [sbeg[q], send[q]) of
+// col / w.  Every singleton joins its strongest neighbour's aggregate (size >= 2)
+// in that order, then the live aggregates are numbered by their smallest node.
+int64_t aggregate_finish(int64_t n, std::vector<int64_t> &agg, const std::vector<int64_t> &size0,
+                         const std::vector<int64_t> &singles, const int64_t *sbeg, const int64_t *send,
+                         const int32_t *col, const double *w, std::vector<int64_t> &agg_of);
+// Where sa_build and find_near_null run the strength graph and the aggregation at
+// strength depth 1 (amg_set_sa_setup): 0 host (default), 1 device (sagraph.hip)
+extern int g_sa_setup;
+constexpr int64_t SG_MAX_ROW = 4096;  // off-diagonal entries of a dof row the device strength graph ranks
+// strength_graph at depth 1 on the device (nn a device block): the node-level graph
+// as a CSR without SpMV storage.  The weight is (t*t)*(t*t) where the host takes
+// std::pow(t, 4.0); everything else gives the host's bits.  A row beyond SG_MAX_ROW:
+// *too_long = true and a null result, or AMG_ERR_UNSUPPORTED when too_long is null.
+CsrPtr strength_graph_device(const CsrOp &A, const double *nn, int64_t ld, int64_t k, const double *w, int64_t bs,
+                             bool *too_long);
+// aggregate_mis of a device graph: the root / claim phase in bounded passes on the
+// device, the tail on the host; past max_passes (0: the default budget) the host
+// sweep on the downloaded graph.  The same result either way.  info4 (optional) =
+// {passes run, roots, singleton roots, fell back (0/1)}
+int64_t aggregate_mis_device(const GpuCsr &G, int64_t max_passes, std::vector<int64_t> &agg_of, int64_t *info4);
 // tentative P for k candidates on nodes of bs dofs (interpolation/mod.rs:754-805)
 CsrPtr sa_tentative_block(Ctx *ctx, int64_t nnodes, int64_t bs, const int64_t *agg_of, int64_t naggs,
                           const double *nn, int64_t ld, int64_t k, int64_t cd, double *coarse_nn);

@@ -464,14 +464,28 @@ void find_near_null(const CsrPtr &A, double *X, int64_t ld, int64_t k, int64_t i
     auto l1 = make_l1(*A);
     smooth_vectors(*A, *l1, B.get(), n, k, iters, nullptr);
     // :288-289 weights, strength graph, aggregates (MIS for the modularity partitioner), BlockSmoother
-    std::vector<double> wts(k), basis(n * k);
+    std::vector<double> wts(k);
     create_weights(*A, B.get(), n, k, wts.data());
-    FAMG_CHECK_HIP(hipMemcpyAsync(basis.data(), B.get(), n * k * sizeof(double), hipMemcpyDeviceToHost, s));
-    FAMG_CHECK_HIP(hipStreamSynchronize(s));
-    B.release();
-    StrengthGraph G = strength_graph(*A, basis.data(), n, k, wts.data(), strength_depth, block_size);
     std::vector<int64_t> agg;
-    const int64_t na = aggregate_mis(G, agg);
+    int64_t na = 0;
+    // amg_set_sa_setup(1) at depth 1: the basis stays on the device (sagraph.hip)
+    CsrPtr Gd;
+    if (g_sa_setup == 1 && strength_depth == 1) {
+        bool too_long = false;
+        Gd = strength_graph_device(*A, B.get(), n, k, wts.data(), block_size, &too_long);
+    }
+    if (Gd) {
+        B.release();
+        na = aggregate_mis_device(Gd->m, 0, agg, nullptr);
+        Gd.reset();
+    } else {
+        std::vector<double> basis(n * k);
+        FAMG_CHECK_HIP(hipMemcpyAsync(basis.data(), B.get(), n * k * sizeof(double), hipMemcpyDeviceToHost, s));
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+        B.release();
+        StrengthGraph G = strength_graph(*A, basis.data(), n, k, wts.data(), strength_depth, block_size);
+        na = aggregate_mis(G, agg);
+    }
     auto blk = make_block_smoother(*A, agg.data(), na, block_size);
     // stage 2 (:290-296) from the caller's start block
     smooth_vectors(*A, *blk, X, ld, k, iters, cfs);

@@ -29,6 +29,7 @@
 // ties in strength are broken by column, ties in MIS degree by node index.
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <numeric>
@@ -199,12 +200,41 @@ StrengthGraph strength_graph(const CsrOp &A, const double *nn, int64_t ld, int64
 
 // ------------------------------------------------------------ aggregation
 
+// The tail of aggregate_mis, which the device path (sagraph.hip) shares: it is
+// order dependent (with an asymmetric pattern a singleton can join an
+// earlier-moved singleton), so it stays one host sweep over the singleton
+// roots' rows.
+int64_t aggregate_finish(int64_t n, std::vector<int64_t> &agg, const std::vector<int64_t> &size0,
+                         const std::vector<int64_t> &singles, const int64_t *sbeg, const int64_t *send,
+                         const int32_t *col, const double *w, std::vector<int64_t> &agg_of) {
+    // singleton roots: join the strongest neighbour's aggregate (size >= 2 before any merge)
+    for (size_t q = 0; q < singles.size(); q++) {
+        const int64_t i = singles[q];
+        int64_t best = -1;
+        double bw = -1.0;
+        for (int64_t e = sbeg[q]; e < send[q]; e++) {
+            const int64_t j = col[e];
+            if (size0[agg[j]] < 2) continue;
+            if (w[e] > bw || (w[e] == bw && j < best)) { bw = w[e]; best = j; }
+        }
+        if (best >= 0) agg[i] = agg[best];
+    }
+    // renumber live aggregates by their smallest node
+    std::vector<int64_t> ren(size0.size(), -1);
+    int64_t na = 0;
+    for (int64_t i = 0; i < n; i++)
+        if (ren[agg[i]] < 0) ren[agg[i]] = na++;
+    agg_of.resize(n);
+    for (int64_t i = 0; i < n; i++) agg_of[i] = ren[agg[i]];
+    return na;
+}
+
 // Aggregates seeded by maximal_independent_set (partitioners/mod.rs:395-423):
 // nodes in descending strength degree (ties: ascending index); a node still
 // free becomes a root and claims every still-free neighbour.  A root that
 // claimed nothing joins the aggregate (of size >= 2) of its strongest
 // neighbour.  Aggregates are numbered by their smallest node.
-int64_t aggregate_mis(const StrengthGraph &G, std::vector<int64_t> &agg_of) {
+int64_t aggregate_mis(const StrengthGraph &G, std::vector<int64_t> &agg_of, int64_t *stats2) {
     const int64_t n = G.n;
     std::vector<double> deg(n, 0.0);
     for (int64_t i = 0; i < n; i++)
@@ -225,33 +255,20 @@ int64_t aggregate_mis(const StrengthGraph &G, std::vector<int64_t> &agg_of) {
             if (agg[j] < 0) { agg[j] = a; size[a]++; }
         }
     }
-    // singleton roots: join the strongest neighbour's aggregate (size >= 2 before any merge)
-    const std::vector<int64_t> size0 = size;
     std::vector<int64_t> singles;
     for (int64_t a = 0; a < (int64_t)roots.size(); a++)
-        if (size0[a] == 1) singles.push_back(roots[a]);
+        if (size[a] == 1) singles.push_back(roots[a]);
     std::sort(singles.begin(), singles.end());
-    for (int64_t i : singles) {
-        int64_t best = -1;
-        double bw = -1.0;
-        for (int64_t e = G.rp[i]; e < G.rp[i + 1]; e++) {
-            const int64_t j = G.col[e];
-            if (size0[agg[j]] < 2) continue;
-            if (G.w[e] > bw || (G.w[e] == bw && j < best)) { bw = G.w[e]; best = j; }
-        }
-        if (best >= 0) {
-            size[agg[i]]--;
-            agg[i] = agg[best];
-        }
+    std::vector<int64_t> sbeg(singles.size()), send(singles.size());
+    for (size_t q = 0; q < singles.size(); q++) {
+        sbeg[q] = G.rp[singles[q]];
+        send[q] = G.rp[singles[q] + 1];
     }
-    // renumber live aggregates by their smallest node
-    std::vector<int64_t> ren(size.size(), -1);
-    int64_t na = 0;
-    for (int64_t i = 0; i < n; i++)
-        if (ren[agg[i]] < 0) ren[agg[i]] = na++;
-    agg_of.resize(n);
-    for (int64_t i = 0; i < n; i++) agg_of[i] = ren[agg[i]];
-    return na;
+    if (stats2) {
+        stats2[0] = (int64_t)roots.size();
+        stats2[1] = (int64_t)singles.size();
+    }
+    return aggregate_finish(n, agg, size, singles, sbeg.data(), send.data(), G.col.data(), G.w.data(), agg_of);
 }
 
 // ------------------------------------------------------------ tentative P
@@ -589,6 +606,27 @@ void nn_postprocess(CsrOp &A, int64_t iters, double *x, int64_t ld, int64_t k) {
 
 // ------------------------------------------------------------ hierarchy
 
+// FAMG_SA_LOG=1: sa_build prints per-level, per-stage wall times to stderr.  A
+// stage ends where the stream has drained, so the clock synchronises it; without
+// the switch it does nothing.
+static bool sa_log_enabled() {
+    static const bool on = env_is_one("FAMG_SA_LOG");
+    return on;
+}
+struct SaStageClock {
+    bool on;
+    hipStream_t s;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double lap() {  // ms since the last lap
+        if (!on) return 0.0;
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+        const auto t1 = std::chrono::steady_clock::now();
+        const double ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t0 = t1;
+        return ms;
+    }
+};
+
 // create_weights (examples/amg/main.rs:571-580): w_c = 1 / (v_c^T A v_c)
 static std::vector<double> default_weights(CsrOp &A, const double *nn, int64_t ld, int64_t k) {
     Ctx &ctx = *A.ctx;
@@ -628,21 +666,57 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
     for (int64_t c = 0; c < k; c++) std::memcpy(nn.data() + c * cur_ld, nn_in + c * ld, A->nrows * sizeof(double));
     int64_t level = 1, coarse_dim = -1, bs = cfg.block_size;
     const int64_t cd = cfg.candidate_dimension;
+    SaStageClock clk{sa_log_enabled(), ctx->stream};
     while ((coarse_dim < 0 || coarse_dim > cfg.coarsest_dim) && level < max_levels) {
         CsrPtr cur = As.back();
         const int64_t n = cur->nrows, nnodes = n / bs;
-        StrengthGraph G = strength_graph(*cur, nn.data(), cur_ld, k, w.data(), cfg.strength_depth, bs);
+        double ms[6] = {0, 0, 0, 0, 0, 0};  // strength, aggregation, tentative P, P smoothing, R + RAP, coarse near-null
+        clk.lap();
         std::vector<int64_t> agg;
-        const int64_t na = aggregate_mis(G, agg);
+        int64_t na = 0, edges = 0, minfo[4] = {0, 0, 0, 0};
+        // policy 1 at depth 1: both stages on the device, the graph staying there (a
+        // row beyond SG_MAX_ROW, like depth > 1, keeps the level on the host)
+        CsrPtr Gd;
+        if (g_sa_setup == 1 && cfg.strength_depth == 1) {
+            DevBuf<double> nnd(std::max<int64_t>(1, n * k));
+            FAMG_CHECK_HIP(hipMemcpy2DAsync(nnd.get(), n * sizeof(double), nn.data(), cur_ld * sizeof(double),
+                                            n * sizeof(double), k, hipMemcpyHostToDevice, ctx->stream));
+            bool too_long = false;
+            Gd = strength_graph_device(*cur, nnd.get(), n, k, w.data(), bs, &too_long);
+        }
+        const bool on_device = Gd != nullptr;
+        if (on_device) {
+            edges = Gd->m.nnz;
+            ms[0] = clk.lap();
+            na = aggregate_mis_device(Gd->m, 0, agg, minfo);
+            Gd.reset();
+        } else {
+            StrengthGraph G = strength_graph(*cur, nn.data(), cur_ld, k, w.data(), cfg.strength_depth, bs);
+            edges = G.rp.back();
+            ms[0] = clk.lap();
+            na = aggregate_mis(G, agg);
+        }
+        ms[1] = clk.lap();
         if (na * cd >= n) break;  // no coarsening left (stall): stop here
         std::vector<double> cnn(na * cd * k);
         CsrPtr P = sa_tentative_block(ctx, nnodes, bs, agg.data(), na, nn.data(), cur_ld, k, cd, cnn.data());
+        ms[2] = clk.lap();
         for (int64_t st = 0; st < cfg.smoothing_steps; st++)
             P = bs == 1 ? smooth_interpolation(*cur, *P, 0.66) : block_jacobi_smooth(*cur, *P, bs, 0.66);
+        ms[3] = clk.lap();
         CsrPtr R = transpose_op(*P);
         CsrPtr Ac = galerkin_rap(*R, *cur, *P);
+        ms[4] = clk.lap();
         nn_postprocess(*Ac, 3, cnn.data(), na * cd, k);
-        if (info) info->push_back({n, bs, nnodes, na, G.rp.back()});
+        ms[5] = clk.lap();
+        if (clk.on)
+            fprintf(stderr,
+                    "famg sa level %lld: n %lld nodes %lld aggregates %lld edges %lld device %d passes %lld fallback %lld"
+                    " ms: strength %.3f aggregation %.3f tentative %.3f smoothing %.3f rap %.3f nearnull %.3f\n",
+                    (long long)(level - 1), (long long)n, (long long)nnodes, (long long)na, (long long)edges,
+                    on_device ? 1 : 0, (long long)minfo[0], (long long)minfo[3], ms[0], ms[1], ms[2], ms[3],
+                    ms[4], ms[5]);
+        if (info) info->push_back({n, bs, nnodes, na, edges});
         aggs.push_back(std::move(agg));
         naggs.push_back(na);
         Rs.push_back(R);
@@ -686,6 +760,7 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
         LinOpPtr S = (l + 1 == As.size()) ? LinOpPtr(make_coarse_chol(*As[l])) : make_smoother(As[l], l);
         mg->add_level(As[l], S, Rs[l - 1], Ps[l - 1]);
     }
+    if (clk.on) fprintf(stderr, "famg sa smoothers: levels %lld ms: smoothers %.3f\n", (long long)As.size(), clk.lap());
     return mg;
 }
 

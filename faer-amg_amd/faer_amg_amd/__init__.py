@@ -178,6 +178,10 @@ SIGNATURES = {
     "amg_sa_build": (i32, [vp, vp, i64, i64, vp, vp, P(vp)]),
     "amg_strength_graph": (i32, [vp, vp, i64, i64, vp, i64, i64, P(vp)]),
     "amg_aggregate_mis": (i32, [vp, vp, P(i64)]),
+    "amg_set_sa_setup": (i32, [i32]),
+    "amg_get_sa_setup": (i32, [P(i32)]),
+    "amg_strength_graph_device": (i32, [vp, vp, i64, i64, vp, i64, C.c_int, P(vp)]),
+    "amg_aggregate_mis_device": (i32, [vp, i64, vp, P(i64), vp]),
     "amg_sa_tentative_block": (i32, [vp, i64, i64, vp, i64, vp, i64, i64, i64, P(vp), vp]),
     "amg_block_jacobi_smooth": (i32, [vp, vp, i64, dbl, P(vp)]),
     "amg_nn_postprocess": (i32, [vp, i64, vp, i64, i64]),
@@ -939,6 +943,56 @@ def aggregate_mis(G):
     na = i64()
     _ck(_lib.amg_aggregate_mis(tmp.h, agg.ctypes.data_as(vp), C.byref(na)))
     return agg, na.value
+
+
+SA_SETUP = {"host": 0, "device": 1}
+
+
+def set_sa_setup(where):
+    """amg_set_sa_setup (process-wide): where amg_sa_build and amg_find_near_null run
+    the strength graph and the aggregation at strength depth 1 -- 'host' / 0 (default)
+    or 'device' / 1.  Not bitwise neutral: the device weighs an edge with (t*t)*(t*t)
+    where the host calls pow(t, 4.0)."""
+    _ck(_lib.amg_set_sa_setup(SA_SETUP[where] if isinstance(where, str) else int(where)))
+
+
+def get_sa_setup():
+    v = i32()
+    _ck(_lib.amg_get_sa_setup(C.byref(v)))
+    return v.value
+
+
+def strength_graph_device(A, near_null, weights, block_size=1):
+    """amg_strength_graph_device: the depth-1 node-level strength graph built on the
+    device, as a SparseMatOp without SpMV storage (read it with .arrays() /
+    .to_scipy(), pass it to aggregate_mis_device).  near_null: n x k, numpy or a
+    column-major torch tensor (host or device)."""
+    if isinstance(near_null, np.ndarray):
+        near_null = _colmajor_host(near_null, A.nrows)
+    p, m, n, k, ld = _dptr(near_null)
+    if n != A.nrows:
+        raise ValueError("near-null space must have one row per matrix row")
+    w = np.ascontiguousarray(weights, np.float64)
+    if len(w) != k:
+        raise ValueError("one weight per near-null column")
+    h = vp()
+    with _ordered(A.ctx, m):
+        _ck(_lib.amg_strength_graph_device(A.h, p, ld, k, w.ctypes.data_as(vp), block_size, m, C.byref(h)))
+    return SparseMatOp(h, A.ctx)
+
+
+def aggregate_mis_device(G, max_passes=0):
+    """amg_aggregate_mis_device of a square SparseMatOp (a strength_graph_device result
+    or an uploaded graph): (agg_of, naggs, info) -- exactly aggregate_mis's aggregates;
+    info = {'passes', 'roots', 'singletons', 'fallback'} (fallback: past max_passes,
+    0 = the default budget, the host sweep ran on the downloaded graph)."""
+    agg = np.zeros(max(G.nrows, 1), np.int64)
+    na = i64()
+    info = np.zeros(4, np.int64)
+    _ck(_lib.amg_aggregate_mis_device(G.h, int(max_passes), agg.ctypes.data_as(vp), C.byref(na),
+                                      info.ctypes.data_as(vp)))
+    return agg[:G.nrows], na.value, {"passes": int(info[0]), "roots": int(info[1]), "singletons": int(info[2]),
+                                     "fallback": bool(info[3])}
 
 
 def _host_csr_from_scipy(G):

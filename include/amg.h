@@ -560,6 +560,48 @@ amg_status amg_block_jacobi_smooth(const amg_linop *A, const amg_linop *P, int64
                                    amg_linop **out);
 amg_status amg_nn_postprocess(const amg_linop *A, int64_t iters, double *x, int64_t ld, int64_t k);
 
+/* Where amg_sa_build (on every level) and amg_find_near_null run the strength
+ * graph and the aggregation (process-wide, like amg_set_spmv_format): 0 host
+ * (default), 1 device (the two functions below; the graph stays on the device
+ * between them, only agg_of comes back).  Not one of the numbered flags: those
+ * are bitwise neutral and this is not -- the device weighs a kept edge with
+ * (t*t)*(t*t) where the host calls pow(t, 4.0) (<= 2 ULP apart; no device code
+ * reproduces libm's pow bit for bit), so a device-built hierarchy is an equally
+ * valid SA hierarchy but not bit-identical to a host-built one.  A level keeps
+ * the host path at strength_depth > 1 (the BFS neighbourhoods are host only) and
+ * when a dof row has more than 4096 off-diagonal entries.  With the policy at 0
+ * nothing changes anywhere.  AMG_ERR_INVALID for another value.
+ * FAMG_SA_LOG=1 makes amg_sa_build print per-level, per-stage wall times to
+ * stderr under either policy. */
+amg_status amg_set_sa_setup(int32_t where);
+amg_status amg_get_sa_setup(int32_t *where);
+/* amg_strength_graph at depth 1 on the device (new_ls_strength_graph,
+ * partitioners/mod.rs:337-393, block-reduced :294-301, :464-497): near_null is
+ * n x k column-major (ld), host or device by `mem`; weights: k host values.  The
+ * node-level graph comes back as a CSR handle on the device (values =
+ * strengths) without SpMV storage: read it with amg_csr_download, pass it to
+ * amg_aggregate_mis_device.  Every step gives the host's bits except the weight
+ * (t*t)*(t*t) (above).  A wave ranks a dof row of <= 256 off-diagonal entries, a
+ * workgroup one of <= 4096; AMG_ERR_UNSUPPORTED beyond. */
+amg_status amg_strength_graph_device(const amg_linop *A, const double *near_null, int64_t ld, int64_t k,
+                                     const double *weights, int64_t block_size, amg_mem mem,
+                                     amg_linop **graph);
+/* amg_aggregate_mis (maximal_independent_set, partitioners/mod.rs:395-423) of a
+ * square CSR handle -- a result of amg_strength_graph_device or a graph uploaded
+ * with amg_csr_create: exactly the host's agg_of (host, n entries) and *naggs.
+ * With u preceding v when its strength degree is larger (ties: the smaller
+ * index) and H(v) the nodes preceding v whose rows list v, v is claimed once some
+ * u in H(v) is a root and a root once every u in H(v) is claimed; bounded passes
+ * over the undecided nodes decide this in place, the host reading the undecided
+ * count every 4 passes (AMG_ERR_INVALID if it stopped falling).  Past max_passes
+ * (0: the default budget, 1024) -- a chain-like graph needs n/2 -- the graph is
+ * downloaded and the host sweep runs: the same result.  The tail (singleton roots
+ * join their strongest neighbour's aggregate, numbering by smallest node) is the
+ * host's own, on the singleton roots' rows only.  info4 (may be NULL) = {passes
+ * run, roots, singleton roots, fell back to the host (0/1)}. */
+amg_status amg_aggregate_mis_device(const amg_linop *graph, int64_t max_passes, int64_t *agg_of,
+                                    int64_t *naggs, int64_t *info4);
+
 /* ---- near-null search (adaptivity.rs:264-390, 434-443) -------------------------
  * From a bare SPD matrix to the candidates amg_sa_build takes, on the device.
  * Blocks are column-major n x k with a leading dimension, 1 <= k <= 64

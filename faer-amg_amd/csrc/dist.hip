@@ -689,21 +689,11 @@ struct DistMultigridOp : LinOp {
     // -- its grouped send/recv and all-gather are stream-ordered and capturable,
     // the loopback transport synchronises on the host
     bool use_graph = false;
-    struct Graph {
-        double *out;
-        const double *rhs;
-        hipGraphExec_t exec;
-    };
-    std::vector<Graph> graphs_;
-    uint64_t flags_gen_ = 0;
-    void drop_graphs() {
-        for (auto &g : graphs_) (void)hipGraphExecDestroy(g.exec);
-        graphs_.clear();
-    }
+    GraphCache graphs_;
     Kind kind() const override { return Kind::DistMultigrid; }
     bool is_precond() const override { return true; }
     ~DistMultigridOp() override {
-        drop_graphs();
+        graphs_.clear();  // before the communication stream they recorded goes
         if (ev_pack) (void)hipEventDestroy(ev_pack);
         if (ev_halo) (void)hipEventDestroy(ev_halo);
         if (comm_stream) (void)hipStreamDestroy(comm_stream);
@@ -801,13 +791,7 @@ struct DistMultigridOp : LinOp {
                     vec_mul(t, D.S->d.get(), f, D.sp.n_own, s);
                 }
             } else {
-                SpmvEpi epi;
-                epi.b = f;
-                epi.d = D.S->d.get();
-                epi.dc = D.S->dcode.get();
-                epi.dt = D.S->dtab.get();
-                epi.dk = D.S->dconst;
-                halo_spmv(D.sp, v, D.A->m, t, SPMV_JACOBI, epi);
+                halo_spmv(D.sp, v, D.A->m, t, SPMV_JACOBI, jacobi_epi(*D.S, f));
             }
             std::swap(v, t);
         }
@@ -846,19 +830,8 @@ struct DistMultigridOp : LinOp {
         // into the tail: one rank restricts straight into the tail's input
         if (tr->nranks != 1 || tail->levels.size() < 2) return false;
         const MgLevel &T = tail->levels[0];
-        auto *Ac = dynamic_cast<const CsrOp *>(T.A.get());
-        auto *Dc = dynamic_cast<const DiagOp *>(T.S.get());
-        auto *Pc = dynamic_cast<const CsrOp *>(T.P.get());
-        return Ac && Dc && !fold_level(Ac, Dc, Pc, tail->fold_zero_guess, true, steps);
-    }
-    static SpmvEpi df_epi(const DiagOp &S, double *y2) {
-        SpmvEpi e;
-        e.d = S.d.get();
-        e.dc = S.dcode.get();
-        e.dt = S.dtab.get();
-        e.dk = S.dconst;
-        e.y2 = y2;
-        return e;
+        return level_wants_df(dynamic_cast<const CsrOp *>(T.A.get()), dynamic_cast<const DiagOp *>(T.S.get()),
+                              dynamic_cast<const CsrOp *>(T.P.get()), tail->fold_zero_guess, steps);
     }
 
     void cycle(int64_t l, double *v, const double *f, bool zero, double *out = nullptr, bool pre_df = false) {
@@ -869,13 +842,7 @@ struct DistMultigridOp : LinOp {
         const bool fold = folds(D, zero);
         SpmvEpi epi;
         epi.b = f;
-        SpmvEpi epi0 = epi;  // the folded epilogues' d*f
-        if (D.S) {
-            epi0.d = D.S->d.get();
-            epi0.dc = D.S->dcode.get();
-            epi0.dt = D.S->dtab.get();
-            epi0.dk = D.S->dconst;
-        }
+        const SpmvEpi epi0 = fold ? jacobi_epi(*D.S, f) : epi;  // the folded epilogues' d*f
         if (fold) {
             log_at(l, AMG_ROLE_RESID);
             spmv(D.A->m, f, D.r.get(), SPMV_RESID0, epi0, s);  // f - A (d f)
@@ -888,7 +855,7 @@ struct DistMultigridOp : LinOp {
         if (l + 1 < La) {
             DLevel &C = L[l + 1];
             log_at(l, AMG_ROLE_RESTRICT);
-            if (df) halo_spmv(D.sp, D.r.get(), D.R->m, C.f.get(), SPMV_SETDF, df_epi(*C.S, C.t.get()));
+            if (df) halo_spmv(D.sp, D.r.get(), D.R->m, C.f.get(), SPMV_SETDF, jacobi_epi(*C.S, nullptr, C.t.get()));
             else halo_spmv(D.sp, D.r.get(), D.R->m, C.f.get(), SPMV_SET, SpmvEpi{});
             for (int64_t k = 0; k < mu; k++) cycle(l + 1, C.v.get(), C.f.get(), k == 0, nullptr, df && k == 0);
             log_at(l, AMG_ROLE_INTERP);
@@ -904,7 +871,8 @@ struct DistMultigridOp : LinOp {
             if (tr->nranks == 1) {  // nothing to gather: restrict into the tail's input
                 if (df)
                     halo_spmv(D.sp, D.r.get(), D.R->m, fc_full.get(), SPMV_SETDF,
-                              df_epi(*dynamic_cast<const DiagOp *>(tail->levels[0].S.get()), tail->levels[0].t.get()));
+                              jacobi_epi(*dynamic_cast<const DiagOp *>(tail->levels[0].S.get()), nullptr,
+                                         tail->levels[0].t.get()));
                 else
                     halo_spmv(D.sp, D.r.get(), D.R->m, fc_full.get(), SPMV_SET, SpmvEpi{});
             } else {
@@ -913,7 +881,7 @@ struct DistMultigridOp : LinOp {
                 gather_tail(gather.get() + tr->rank * tail_max);
             }
             if (g_launch_log) g_launch_log->level_base = (int32_t)La;
-            for (int64_t k = 0; k < mu; k++) tail->cycle(0, vc_full.get(), fc_full.get(), k == 0, nullptr, df && k == 0);
+            for (int64_t k = 0; k < mu; k++) tail->cycle(0, vc_full.get(), fc_full.get(), k == 0, df && k == 0);
             if (g_launch_log) g_launch_log->level_base = 0;
             log_at(l, AMG_ROLE_INTERP);
             if (fold) {
@@ -973,40 +941,9 @@ struct DistMultigridOp : LinOp {
 
     void apply(double *out, const double *rhs) override {
         std::lock_guard<std::mutex> lk(mtx);
-        hipStream_t s = ctx->stream;
         tail->ensure_workspace();
-        if (flags_gen_ != flags_generation()) {  // a switch changed: graphs recorded the old launches
-            drop_graphs();
-            flags_gen_ = flags_generation();
-        }
-        if (!use_graph || !dynamic_cast<RcclTransport *>(tr.get())) {
-            apply_eager(out, rhs);
-            return;
-        }
-        for (auto &g : graphs_)
-            if (g.out == out && g.rhs == rhs) {
-                FAMG_CHECK_HIP(hipGraphLaunch(g.exec, s));
-                return;
-            }
-        hipGraph_t graph = nullptr;
-        FAMG_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        try {
-            apply_eager(out, rhs);
-        } catch (...) {
-            (void)hipStreamEndCapture(s, &graph);
-            if (graph) (void)hipGraphDestroy(graph);
-            throw;
-        }
-        FAMG_CHECK_HIP(hipStreamEndCapture(s, &graph));
-        hipGraphExec_t exec = nullptr;
-        FAMG_CHECK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(graph);
-        if (graphs_.size() >= 8) {
-            (void)hipGraphExecDestroy(graphs_.front().exec);
-            graphs_.erase(graphs_.begin());
-        }
-        graphs_.push_back({out, rhs, exec});
-        FAMG_CHECK_HIP(hipGraphLaunch(exec, s));
+        if (!use_graph || !dynamic_cast<RcclTransport *>(tr.get())) apply_eager(out, rhs);
+        else graphs_.launch(out, rhs, ctx->stream, [&] { apply_eager(out, rhs); });
     }
 
     // launch records of one eager cycle on scratch vectors (amg_dist_cycle_plan)
@@ -1029,7 +966,7 @@ struct DistMultigridOp : LinOp {
         hipStream_t s = ctx->stream;
         if (La == 0) {
             gather_tail(rhs);
-            tail->cycle(0, vc_full.get(), fc_full.get(), true, nullptr);
+            tail->cycle(0, vc_full.get(), fc_full.get(), true);
             const int64_t r0 = tail_splits[tr->rank], cnt = tail_splits[tr->rank + 1] - r0;
             if (cnt) vec_copy(out, vc_full.get() + r0, cnt, s);
             return;
@@ -1514,9 +1451,9 @@ amg_status amg_dist_set_option(amg_linop *dist, int32_t option, int64_t value) {
         auto d = need_dist(dist);
         std::lock_guard<std::mutex> lk(d->mtx);
         switch (option) {
-        case 0: d->overlap = value != 0; d->drop_graphs(); break;
-        case 1: d->use_graph = value != 0; d->drop_graphs(); break;
-        case 2: d->per_colour_halo = value != 0; d->drop_graphs(); break;
+        case 0: d->overlap = value != 0; d->graphs_.clear(); break;
+        case 1: d->use_graph = value != 0; d->graphs_.clear(); break;
+        case 2: d->per_colour_halo = value != 0; d->graphs_.clear(); break;
         default: fail(AMG_ERR_INVALID, "unknown distributed multigrid option");
         }
     });

@@ -627,6 +627,19 @@ struct DiagOp : LinOp {
     void apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) override;  // one k-wide scale
     void apply_in_place(double *rhs) override;
 };
+// the SpMV epilogue of a Jacobi step with D: d with its 8-bit codes (gathered instead
+// of d where the kernel reads them) and its one value; b for JACOBI / RESID0 / ADD0,
+// y2 for SETDF
+inline SpmvEpi jacobi_epi(const DiagOp &D, const double *b = nullptr, double *y2 = nullptr) {
+    SpmvEpi e;
+    e.b = b;
+    e.d = D.d.get();
+    e.dc = D.dcode.get();
+    e.dt = D.dtab.get();
+    e.dk = D.dconst;
+    e.y2 = y2;
+    return e;
+}
 
 struct SgsOp : LinOp {
     CsrPtr A;              // original operator
@@ -725,6 +738,79 @@ struct MgLevel {
 };
 constexpr int64_t MG_BLOCK_COLS = 32;  // widest block one block cycle takes; wider blocks run in chunks
 
+// hipGraph replay of one cycle per (out, rhs) pair: the 8 most recently captured pairs.
+// Whether to replay at all stays with the owner (MultigridOp / DistMultigridOp::apply).
+class GraphCache {
+  public:
+    GraphCache() = default;
+    GraphCache(const GraphCache &) = delete;
+    GraphCache &operator=(const GraphCache &) = delete;
+    ~GraphCache() { clear(); }
+    // drop every graph: what they recorded (operators, options, workspaces) changed
+    void clear() {
+        for (auto &g : graphs_) (void)hipGraphExecDestroy(g.exec);
+        graphs_.clear();
+    }
+    // a run-time switch changed since the last call (the graphs recorded the old
+    // launches, so they are dropped)
+    bool flags_moved() {
+        if (gen_ == flags_generation()) return false;
+        clear();
+        gen_ = flags_generation();
+        return true;
+    }
+    // replay the graph of (out, rhs) on s; without one, capture what body() issues on
+    // s, keep it in place of the oldest of 8, and launch it
+    template <class F> void launch(double *out, const double *rhs, hipStream_t s, F &&body) {
+        flags_moved();
+        for (auto &g : graphs_)
+            if (g.out == out && g.rhs == rhs) {
+                FAMG_CHECK_HIP(hipGraphLaunch(g.exec, s));
+                return;
+            }
+        hipGraph_t graph = nullptr;
+        FAMG_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        try {
+            body();
+        } catch (...) {
+            (void)hipStreamEndCapture(s, &graph);
+            if (graph) (void)hipGraphDestroy(graph);
+            throw;
+        }
+        FAMG_CHECK_HIP(hipStreamEndCapture(s, &graph));
+        hipGraphExec_t exec = nullptr;
+        FAMG_CHECK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(graph);
+        if (graphs_.size() >= 8) {
+            (void)hipGraphExecDestroy(graphs_.front().exec);
+            graphs_.erase(graphs_.begin());
+        }
+        graphs_.push_back({out, rhs, exec});
+        FAMG_CHECK_HIP(hipGraphLaunch(exec, s));
+    }
+
+  private:
+    struct Entry {
+        double *out;
+        const double *rhs;
+        hipGraphExec_t exec;
+    };
+    std::vector<Entry> graphs_;
+    uint64_t gen_ = 0;  // flags_generation() the graphs were captured under
+};
+
+// How level l takes its step of the V-cycle (MultigridOp::level_shape): decided in one
+// place because producers and consumers of d*f must agree -- smooth() skips that pass
+// on its caller's word (pre_df), so a disagreement is a wrong cycle, not an error.
+struct LevelShape {
+    const CsrOp *A = nullptr, *R = nullptr, *P = nullptr;  // the level's operators where they are CSR
+    bool fold = false;     // the zero-guess Jacobi step folded into RESID0 + ADD0 (fold_level)
+    bool df = false;       // R also writes level l + 1's first Jacobi step d_c f_c (SPMV_SETDF)
+    bool fuse_rr = false;  // folded residual + restriction as one marching launch (fine.hip)
+    bool fuse_pj = false;  // interpolation + post-smoothing as one
+    SpmvEpi epi0, epic;    // fold: d*f of this level's f / df: d_c and where d_c f_c goes
+};
+
 struct MultigridOp : LinOp {
     std::vector<MgLevel> levels;
     int64_t mu = 1, steps = 1;
@@ -759,7 +845,10 @@ struct MultigridOp : LinOp {
     // V-cycle building blocks (also used by the distributed multigrid)
     // pre_df: the restriction that produced f already wrote the first Jacobi
     // step from zero (d*f, SPMV_SETDF) into the level's t buffer
-    void cycle(int64_t l, double *v, const double *f, bool v_zero, double *out_final, bool pre_df = false);
+    void cycle(int64_t l, double *v, const double *f, bool v_zero, bool pre_df = false);
+    // the shape of level l < L - 1 entered with right-hand side f (not kept across
+    // calls: operators, options and switches may change in between)
+    LevelShape level_shape(int64_t l, const double *f, bool v_zero) const;
     void smooth(int64_t l, double *&v, double *&t, const double *f, bool v_zero, bool pre_df = false);
     // the renumbered fine level's rhs gather, with its first Jacobi step from zero
     // written beside it where the level takes that step unfolded
@@ -790,17 +879,15 @@ struct MultigridOp : LinOp {
     hipEvent_t fine_ev[2] = {nullptr, nullptr};
 
   private:
-    struct GraphEntry {
-        double *out;
-        const double *rhs;
-        hipGraphExec_t exec;
-    };
-    std::vector<GraphEntry> graphs_;
-    uint64_t flags_gen_ = 0;  // flags_generation() the graphs were captured under
+    GraphCache graphs_;
     bool workspace_ready_ = false;
     bool reorder_done_ = false;
+    // before any cycle is issued: the hierarchy's invariants, the workspaces, graphs and
+    // dense tail of the current switches
+    void prepare();
+    void run_cycle(double *out, const double *rhs);  // one cycle on the stream, renumbered fine level or not
     void ensure_block_workspace(int64_t kw);
-    void block_check(int64_t kw);  // apply()'s invariants, workspaces for kw columns, the dense tail
+    void block_check(int64_t kw);  // prepare() and the workspaces for kw columns
     void block_run(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t kw);
     void block_cycle(int64_t l, double *V, int64_t ldv, const double *F, int64_t ldf, int64_t kw, bool v_zero);
     void block_smooth(int64_t l, double *&V, int64_t &ldv, double *&T, int64_t &ldt, const double *F, int64_t ldf,
@@ -831,6 +918,11 @@ void perm_gather_df(double *f0, double *t, const double *in, const int32_t *p, c
 // even), truncated at the faces: fills m.dia_cst* (sgs27.hip)
 bool dia_constant(GpuCsr &m);
 bool fold_level(const CsrOp *A, const DiagOp *D, const CsrOp *P, bool fold_zero_guess, bool v_zero, int64_t steps);
+// the level takes its first Jacobi step from zero unfolded (smooth(): t = d*f), so
+// whoever produces its f may write that step beside it
+inline bool level_wants_df(const CsrOp *A, const DiagOp *D, const CsrOp *P, bool fold_zero_guess, int64_t steps) {
+    return A && D && steps >= 1 && !fold_level(A, D, P, fold_zero_guess, true, steps);
+}
 // the restriction into a level writes that level's first Jacobi step from zero
 // (SPMV_SETDF) -- false with FAMG_SETDF=0
 bool setdf_enabled();

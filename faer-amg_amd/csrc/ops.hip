@@ -427,13 +427,11 @@ void CoarseCholOp::apply_block(double *out, int64_t ldo, const double *rhs, int6
 // --------------------------------------------------------------- multigrid
 
 MultigridOp::~MultigridOp() {
-    invalidate_graphs();
     for (auto &e : fine_ev)
         if (e) (void)hipEventDestroy(e);
 }
 
 void MultigridOp::invalidate_graphs() {
-    for (auto &g : graphs_) (void)hipGraphExecDestroy(g.exec);
     graphs_.clear();
     tail_key_ = ~uint64_t(0);  // operators, options or switches changed: the dense tail is rebuilt
 }
@@ -518,13 +516,7 @@ void MultigridOp::smooth(int64_t l, double *&v, double *&t, const double *f, boo
                 if (D->dcode.get()) vec_mul_coded(t, D->dcode.get(), D->dtab.get(), f, n, s);
                 else vec_mul(t, D->d.get(), f, n, s);  // 0 + d (f - A 0)
             } else {
-                SpmvEpi epi;
-                epi.b = f;
-                epi.d = D->d.get();
-                epi.dc = D->dcode.get();
-                epi.dt = D->dtab.get();
-                epi.dk = D->dconst;
-                spmv(A->m, v, t, SPMV_JACOBI, epi, s);
+                spmv(A->m, v, t, SPMV_JACOBI, jacobi_epi(*D, f), s);
             }
             std::swap(v, t);
         } else if (A && G) {
@@ -565,8 +557,18 @@ void MultigridOp::smooth(int64_t l, double *&v, double *&t, const double *f, boo
 // One Jacobi step from v = 0 gives v = d*f; with s = 1 nothing else reads v
 // before the correction, so the residual gathers d*f on the fly (RESID0) and the
 // correction writes d*f + P v_c (ADD0): the same rounded values, 16n bytes and
-// one launch fewer per level.  Where that pays (measured per storage, below) --
-// the decision of MultigridOp::cycle and of the distributed cycle's levels.
+// one launch fewer per level.  Where that pays (measured per storage) -- the
+// decision of MultigridOp::level_shape and of the distributed cycle's levels.
+// Only for bandwidth-bound storage (SELL with fp64 values): value-code SELL and
+// the wave-per-row kernel are latency-bound, and gathering d beside x cost more
+// there than the separate streaming pass (measured on the 256^3 hierarchy).
+// DIA storage folds where P runs the short-slice kernel (P_0 of the 256^3
+// cycle): the residual gathers d beside x (115 us vs 91 + 51 for RESID + the
+// d*f pass) and the correction's d*f epilogue costs 117 vs 99 us -- 9 us net.
+// With the generic value-code SELL P (level 1) it lost: 58 + 49 vs 44 + 9 + 46.
+// Not where most slices carry 32-bit columns (unstructured operators): the
+// residual then gathers d as randomly as x, and that doubled gather cost more
+// than the pass it saves (Q1 elasticity 1.57M rows: 640 vs 388 + 15 us).
 bool fold_level(const CsrOp *A, const DiagOp *D, const CsrOp *P, bool fold_zero_guess, bool v_zero, int64_t steps) {
     const bool gather_cheap = A && 2 * A->m.sell_mode_slices[2] < A->m.nslices;
     // x-staged stencil classes (levels 1-3 of the box hierarchies): d*f can be
@@ -613,13 +615,13 @@ void MultigridOp::gather_fine(const double *rhs, hipStream_t s) {
     auto *A = dynamic_cast<CsrOp *>(L.A.get());
     auto *D = dynamic_cast<DiagOp *>(L.S.get());
     auto *P = dynamic_cast<CsrOp *>(L.P.get());
-    const bool df = levels.size() > 1 && A && D && steps >= 1 && !fold_level(A, D, P, fold_zero_guess, true, steps);
+    const bool df = levels.size() > 1 && level_wants_df(A, D, P, fold_zero_guess, steps);
     if (df) {
         perm_gather_df(perm_f0_.get(), L.t.get(), rhs, L.perm.get(), *D, n, s);
     } else {
         perm_gather(perm_f0_.get(), rhs, L.perm.get(), n, s);
     }
-    cycle(0, perm_v0_.get(), perm_f0_.get(), true, perm_v0_.get(), df);
+    cycle(0, perm_v0_.get(), perm_f0_.get(), true, df);
 }
 
 void MultigridOp::ensure_tail() {
@@ -646,7 +648,7 @@ void MultigridOp::ensure_tail() {
         LaunchLogScope mute(nullptr);
         for (int64_t j = 0; j < n; j++) {
             unit_vector(e.get(), n, j, s);
-            cycle(l0, Mt.get() + j * n, e.get(), true, nullptr, false);
+            cycle(l0, Mt.get() + j * n, e.get(), true);
         }
     }
     tail_M_.resize(n * n);
@@ -655,7 +657,33 @@ void MultigridOp::ensure_tail() {
     tail_level = l0;
 }
 
-void MultigridOp::cycle(int64_t l, double *v, const double *f, bool v_zero, double *, bool pre_df) {
+LevelShape MultigridOp::level_shape(int64_t l, const double *f, bool v_zero) const {
+    const MgLevel &L = levels[l], &C = levels[l + 1];
+    LevelShape sh;
+    sh.A = dynamic_cast<const CsrOp *>(L.A.get());
+    sh.R = dynamic_cast<const CsrOp *>(L.R.get());
+    sh.P = dynamic_cast<const CsrOp *>(L.P.get());
+    auto *D = dynamic_cast<const DiagOp *>(L.S.get());
+    sh.fold = fold_level(sh.A, D, sh.P, fold_zero_guess, v_zero, steps);
+    if (sh.fold) sh.epi0 = jacobi_epi(*D, f);  // (DIA: 1-B codes of d gathered instead of d)
+    // R on grid-transfer classes (either width) also writes the next level's first Jacobi
+    // step from zero (d_c * f_c, what smooth() would compute first) into the
+    // buffer that step writes: one launch and 24 n_c bytes fewer, same values.
+    // Not into the coarsest level (no Jacobi step) nor the dense tail (its GEMV never reads C.t).
+    if (l + 2 < (int64_t)levels.size() && l + 1 != tail_level && restrict_df && setdf_enabled() &&
+        r_has_setdf(sh.R)) {
+        auto *Dc = dynamic_cast<const DiagOp *>(C.S.get());
+        sh.df = level_wants_df(dynamic_cast<const CsrOp *>(C.A.get()), Dc, dynamic_cast<const CsrOp *>(C.P.get()),
+                               fold_zero_guess, steps);
+        // y2 = C.t: cycle(l + 1, C.v, ...) smooths into C.t first
+        if (sh.df) sh.epic = jacobi_epi(*Dc, nullptr, C.t.get());
+    }
+    sh.fuse_rr = sh.fold && sh.df && fine_resid_restrict_ok(sh.A->m, sh.R->m, sh.epi0, sh.epic);
+    sh.fuse_pj = sh.fold && steps == 1 && fine_interp_jacobi_ok(sh.A->m, sh.P->m, sh.epi0);
+    return sh;
+}
+
+void MultigridOp::cycle(int64_t l, double *v, const double *f, bool v_zero, bool pre_df) {
     MgLevel &L = levels[l];
     hipStream_t s = ctx->stream;
     const int64_t n = L.A->nrows;
@@ -671,101 +699,50 @@ void MultigridOp::cycle(int64_t l, double *v, const double *f, bool v_zero, doub
     }
     double *v0 = v;
     double *t = (v == L.t.get()) ? L.v.get() : L.t.get();
-    auto *A = dynamic_cast<CsrOp *>(L.A.get());
-    auto *D = dynamic_cast<DiagOp *>(L.S.get());
-    auto *P = dynamic_cast<CsrOp *>(L.P.get());
-    // One Jacobi step from v = 0 gives v = d*f; with s = 1 nothing else reads
-    // v before the correction, so the residual gathers d*f on the fly and the
-    // correction writes d*f + P v_c: the same rounded values, 16n bytes and one
-    // launch fewer per level.  Only for bandwidth-bound storage (SELL with fp64
-    // values): value-code SELL and the wave-per-row kernel are latency-bound,
-    // and gathering d beside x cost more there than the separate streaming
-    // pass (measured on the 256^3 hierarchy).
-    // DIA storage folds where P runs the short-slice kernel (P_0 of the 256^3
-    // cycle): the residual gathers d beside x (115 us vs 91 + 51 for RESID + the
-    // d*f pass) and the correction's d*f epilogue costs 117 vs 99 us -- 9 us net.
-    // With the generic value-code SELL P (level 1) it lost: 58 + 49 vs 44 + 9 + 46.
-    // Not where most slices carry 32-bit columns (unstructured operators): the
-    // residual then gathers d as randomly as x, and that doubled gather cost more
-    // than the pass it saves (Q1 elasticity 1.57M rows: 640 vs 388 + 15 us).
-    const bool fold = fold_level(A, D, P, fold_zero_guess, v_zero, steps);
+    const LevelShape sh = level_shape(l, f, v_zero);
     MgLevel &C = levels[l + 1];
-    // R on grid-transfer classes (either width) also writes the next level's first Jacobi
-    // step from zero (d_c * f_c, what smooth() would compute first) into the
-    // buffer that step writes: one launch and 24 n_c bytes fewer, same values
-    bool df = false;
-    auto *Rc = dynamic_cast<CsrOp *>(L.R.get());
-    SpmvEpi epic;  // the SETDF epilogue: level l + 1's d, y2 = d_c f_c
-    if (l + 2 < (int64_t)levels.size() && l + 1 != tail_level && restrict_df && setdf_enabled()) {
-        auto *Ac = dynamic_cast<CsrOp *>(C.A.get());
-        auto *Dc = dynamic_cast<DiagOp *>(C.S.get());
-        auto *Pc = dynamic_cast<CsrOp *>(C.P.get());
-        df = r_has_setdf(Rc) && Ac && Dc && steps >= 1 &&
-             !fold_level(Ac, Dc, Pc, fold_zero_guess, true, steps);
-        if (df) {
-            epic.d = Dc->d.get();
-            epic.dc = Dc->dcode.get();
-            epic.dt = Dc->dtab.get();
-            epic.dk = Dc->dconst;
-            epic.y2 = C.t.get();  // cycle(l + 1, C.v, ...) smooths into C.t first
-        }
-    }
-    SpmvEpi epi0;  // the folded residual's epilogue
-    if (fold) {
-        epi0.b = f;
-        epi0.d = D->d.get();
-        epi0.dc = D->dcode.get();  // DIA: 1-B codes of d gathered instead of d
-        epi0.dt = D->dtab.get();
-        epi0.dk = D->dconst;
-    }
-    if (fold && df && fine_resid_restrict_ok(A->m, Rc->m, epi0, epic)) {
+    if (sh.fuse_rr) {
         // the folded residual and the restriction in one marching launch
         // (fine.hip): r stays in LDS, f_c and d_c f_c land where SETDF writes them
         log_at(l, AMG_ROLE_RESID);
         if (fine_timer == 0) FAMG_CHECK_HIP(hipEventRecord(fine_ev[0], s));
-        fine_resid_restrict(A->m, Rc->m, f, D->dconst, C.f.get(), epic, s);
+        fine_resid_restrict(sh.A->m, sh.R->m, f, sh.epi0.dk, C.f.get(), sh.epic, s);
         if (fine_timer == 0) FAMG_CHECK_HIP(hipEventRecord(fine_ev[1], s));
     } else {
-        if (fold) {
+        if (sh.fold) {
             log_at(l, AMG_ROLE_RESID);
-            spmv(A->m, f, L.r.get(), SPMV_RESID0, epi0, s);  // work = f - A (d f)
+            spmv(sh.A->m, f, L.r.get(), SPMV_RESID0, sh.epi0, s);  // work = f - A (d f)
         } else {
             smooth(l, v, t, f, v_zero, pre_df);
             log_at(l, AMG_ROLE_RESID);
-            if (A) {
+            if (sh.A) {
                 SpmvEpi epi;
                 epi.b = f;
-                spmv(A->m, v, L.r.get(), SPMV_RESID, epi, s);  // work = f - A v (:341-342)
+                spmv(sh.A->m, v, L.r.get(), SPMV_RESID, epi, s);  // work = f - A v (:341-342)
             } else {
                 L.A->apply(L.r.get(), v);
                 vec_sub(L.r.get(), f, L.r.get(), n, s);
             }
         }
         log_at(l, AMG_ROLE_RESTRICT);
-        if (df) spmv(Rc->m, L.r.get(), C.f.get(), SPMV_SETDF, epic, s);
+        if (sh.df) spmv(sh.R->m, L.r.get(), C.f.get(), SPMV_SETDF, sh.epic, s);
         else L.R->apply(C.f.get(), L.r.get());  // f_c = R work (:343)
     }
-    for (int64_t k = 0; k < mu; k++) cycle(l + 1, C.v.get(), C.f.get(), k == 0, nullptr, df && k == 0);
+    for (int64_t k = 0; k < mu; k++) cycle(l + 1, C.v.get(), C.f.get(), k == 0, sh.df && k == 0);
     log_at(l, AMG_ROLE_INTERP);
-    if (fold) {
-        SpmvEpi epi;
-        epi.b = f;
-        epi.d = D->d.get();
-        epi.dc = D->dcode.get();
-        epi.dt = D->dtab.get();
-        epi.dk = D->dconst;
-        if (steps == 1 && fine_interp_jacobi_ok(A->m, P->m, epi)) {
-            // v = d f + P v_c and the post-smoothing step in one marching launch
-            // (fine.hip): v stays in LDS, the result lands in v0
-            if (fine_timer == 1) FAMG_CHECK_HIP(hipEventRecord(fine_ev[0], s));
-            fine_interp_jacobi(A->m, P->m, C.v.get(), f, D->dconst, v0, s);
-            if (fine_timer == 1) FAMG_CHECK_HIP(hipEventRecord(fine_ev[1], s));
-            return;
-        }
-        spmv(P->m, C.v.get(), t, SPMV_ADD0, epi, s);  // v = d f + P v_c
-        std::swap(v, t);                               // (where smooth() would have left v)
-    } else if (P) {
-        spmv(P->m, C.v.get(), v, SPMV_ADD, SpmvEpi{}, s);  // v += P v_c (:349-350)
+    if (sh.fuse_pj) {
+        // v = d f + P v_c and the post-smoothing step in one marching launch
+        // (fine.hip): v stays in LDS, the result lands in v0
+        if (fine_timer == 1) FAMG_CHECK_HIP(hipEventRecord(fine_ev[0], s));
+        fine_interp_jacobi(sh.A->m, sh.P->m, C.v.get(), f, sh.epi0.dk, v0, s);
+        if (fine_timer == 1) FAMG_CHECK_HIP(hipEventRecord(fine_ev[1], s));
+        return;
+    }
+    if (sh.fold) {
+        spmv(sh.P->m, C.v.get(), t, SPMV_ADD0, sh.epi0, s);  // v = d f + P v_c
+        std::swap(v, t);                                      // (where smooth() would have left v)
+    } else if (sh.P) {
+        spmv(sh.P->m, C.v.get(), v, SPMV_ADD, SpmvEpi{}, s);  // v += P v_c (:349-350)
     } else {
         L.P->apply(L.r.get(), C.v.get());
         vec_add_inplace(v, L.r.get(), n, s);
@@ -777,118 +754,61 @@ void MultigridOp::cycle(int64_t l, double *v, const double *f, bool v_zero, doub
 
 bool MultigridOp::fine_launch(int which, double *out, const double *rhs) {
     std::lock_guard<std::mutex> lk(mtx);
-    ensure_workspace();
-    if (levels.size() < 3 || levels[0].permuted) return false;
-    MgLevel &L = levels[0], &C = levels[1];
-    auto *A = dynamic_cast<CsrOp *>(L.A.get());
-    auto *D = dynamic_cast<DiagOp *>(L.S.get());
-    auto *P = dynamic_cast<CsrOp *>(L.P.get());
-    auto *Rc = dynamic_cast<CsrOp *>(L.R.get());
-    if (!A || !D || !P || !Rc || !fold_level(A, D, P, fold_zero_guess, true, steps) || steps != 1) return false;
-    SpmvEpi epi0;
-    epi0.b = rhs;
-    epi0.d = D->d.get();
-    epi0.dc = D->dcode.get();
-    epi0.dt = D->dtab.get();
-    epi0.dk = D->dconst;
-    hipStream_t s = ctx->stream;
-    if (which == 1) {
-        if (!fine_interp_jacobi_ok(A->m, P->m, epi0)) return false;
-        fine_interp_jacobi(A->m, P->m, C.v.get(), rhs, D->dconst, out, s);
-        return true;
-    }
-    auto *Ac = dynamic_cast<CsrOp *>(C.A.get());
-    auto *Dc = dynamic_cast<DiagOp *>(C.S.get());
-    auto *Pc = dynamic_cast<CsrOp *>(C.P.get());
-    if (!(restrict_df && setdf_enabled() && r_has_setdf(Rc) && Ac && Dc &&
-          !fold_level(Ac, Dc, Pc, fold_zero_guess, true, steps)))
-        return false;
-    SpmvEpi epic;
-    epic.d = Dc->d.get();
-    epic.dc = Dc->dcode.get();
-    epic.dt = Dc->dtab.get();
-    epic.dk = Dc->dconst;
-    epic.y2 = C.t.get();
-    if (!fine_resid_restrict_ok(A->m, Rc->m, epi0, epic)) return false;
-    fine_resid_restrict(A->m, Rc->m, rhs, D->dconst, C.f.get(), epic, s);
+    prepare();
+    // (out and rhs are in the caller's numbering, and a renumbered level never fuses)
+    if (levels.size() < 2 || levels[0].permuted) return false;
+    const LevelShape sh = level_shape(0, rhs, true);
+    if (!(which == 1 ? sh.fuse_pj : sh.fuse_rr)) return false;
+    MgLevel &C = levels[1];
+    if (which == 1) fine_interp_jacobi(sh.A->m, sh.P->m, C.v.get(), rhs, sh.epi0.dk, out, ctx->stream);
+    else fine_resid_restrict(sh.A->m, sh.R->m, rhs, sh.epi0.dk, C.f.get(), sh.epic, ctx->stream);
     return true;
+}
+
+void MultigridOp::prepare() {
+    FAMG_REQUIRE(!levels.empty(), AMG_ERR_INVALID, "empty multigrid");
+    for (size_t l = 0; l + 1 < levels.size(); l++)
+        FAMG_REQUIRE(levels[l].R && levels[l].P, AMG_ERR_INVALID, "multigrid level without R/P");
+    ensure_workspace();
+    if (graphs_.flags_moved()) invalidate_graphs();  // a switch changed: the dense tail is rebuilt too
+    ensure_tail();
+}
+
+void MultigridOp::run_cycle(double *out, const double *rhs) {
+    hipStream_t s = ctx->stream;
+    if (levels[0].permuted) {  // the fine level runs in its numbering: rhs in, result out
+        gather_fine(rhs, s);
+        perm_scatter(out, perm_v0_.get(), levels[0].perm.get(), levels[0].A->nrows, s);
+    } else {
+        cycle(0, out, rhs, true);
+    }
 }
 
 // LinOp::apply for Multigrid (multigrid.rs:469-473 / init_cycle :251-267):
 // out = V-cycle(rhs) from a zero guess.
 void MultigridOp::apply(double *out, const double *rhs) {
     std::lock_guard<std::mutex> lk(mtx);
-    FAMG_REQUIRE(!levels.empty(), AMG_ERR_INVALID, "empty multigrid");
     FAMG_REQUIRE(out != rhs, AMG_ERR_INVALID, "multigrid apply: out must not alias rhs");
-    for (size_t l = 0; l + 1 < levels.size(); l++)
-        FAMG_REQUIRE(levels[l].R && levels[l].P, AMG_ERR_INVALID, "multigrid level without R/P");
-    ensure_workspace();
-    if (flags_gen_ != flags_generation()) {  // a switch changed: graphs recorded the old launches
-        invalidate_graphs();
-        flags_gen_ = flags_generation();
-    }
-    ensure_tail();
+    prepare();
     hipStream_t s = ctx->stream;
-    auto run = [&]() {
-        if (levels[0].permuted) {  // the fine level runs in its numbering: rhs in, result out
-            const int64_t n = levels[0].A->nrows;
-            gather_fine(rhs, s);
-            perm_scatter(out, perm_v0_.get(), levels[0].perm.get(), n, s);
-        } else {
-            cycle(0, out, rhs, true, out);
-        }
-    };
     // (the in-cycle launch timer runs the cycle eagerly: events recorded by graph
     // nodes cannot be read back with hipEventElapsedTime)
-    if (!use_graph || s == nullptr || fine_timer >= 0) {
-        run();
-        return;
-    }
-    for (auto &g : graphs_)
-        if (g.out == out && g.rhs == rhs) {
-            FAMG_CHECK_HIP(hipGraphLaunch(g.exec, s));
-            return;
-        }
-    hipGraph_t graph = nullptr;
-    FAMG_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    try {
-        run();
-    } catch (...) {
-        (void)hipStreamEndCapture(s, &graph);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
-    }
-    FAMG_CHECK_HIP(hipStreamEndCapture(s, &graph));
-    hipGraphExec_t exec = nullptr;
-    FAMG_CHECK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    if (graphs_.size() >= 8) {
-        (void)hipGraphExecDestroy(graphs_.front().exec);
-        graphs_.erase(graphs_.begin());
-    }
-    graphs_.push_back({out, rhs, exec});
-    FAMG_CHECK_HIP(hipGraphLaunch(exec, s));
+    if (!use_graph || s == nullptr || fine_timer >= 0) run_cycle(out, rhs);
+    else graphs_.launch(out, rhs, s, [&] { run_cycle(out, rhs); });
 }
 
 // Launch plan of one V-cycle (amg_multigrid_cycle_plan): one eager cycle on
 // scratch vectors (b = 1) with the launch recorder on.
 std::vector<LaunchRec> MultigridOp::cycle_plan() {
     std::lock_guard<std::mutex> lk(mtx);
-    FAMG_REQUIRE(!levels.empty(), AMG_ERR_INVALID, "empty multigrid");
-    ensure_workspace();
-    ensure_tail();
+    prepare();
     const int64_t n = levels[0].A->nrows;
     DevBuf<double> b(std::max<int64_t>(1, n)), z(std::max<int64_t>(1, n));
     vec_fill(b.get(), 1.0, n, ctx->stream);
     LaunchLog log;
     {
         LaunchLogScope scope(&log);
-        if (levels[0].permuted) {
-            gather_fine(b.get(), ctx->stream);
-            perm_scatter(z.get(), perm_v0_.get(), levels[0].perm.get(), n, ctx->stream);
-        } else {
-            cycle(0, z.get(), b.get(), true, z.get());
-        }
+        run_cycle(z.get(), b.get());
     }
     FAMG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return log.recs;
@@ -1020,15 +940,7 @@ void MultigridOp::block_cycle(int64_t l, double *V, int64_t ldv, const double *F
 }
 
 void MultigridOp::block_check(int64_t kw) {
-    FAMG_REQUIRE(!levels.empty(), AMG_ERR_INVALID, "empty multigrid");
-    for (size_t l = 0; l + 1 < levels.size(); l++)
-        FAMG_REQUIRE(levels[l].R && levels[l].P, AMG_ERR_INVALID, "multigrid level without R/P");
-    ensure_workspace();
-    if (flags_gen_ != flags_generation()) {
-        invalidate_graphs();
-        flags_gen_ = flags_generation();
-    }
-    ensure_tail();
+    prepare();
     ensure_block_workspace(kw);
 }
 

@@ -1819,6 +1819,106 @@ def test_fine_timer_in_cycle(ctx):
         assert torch.equal(z0, z1)
 
 
+@pytest.mark.parametrize("dims,tail_rows", [((64, 64, 64), 4096), ((32, 32, 8), 4096), ((64, 64, 16), 8192)])
+def test_fine_launch_matches_cycle(ctx, dims, tail_rows):
+    """amg_multigrid_fine_launch makes a fused fine-level launch exactly where the
+    cycle makes it -- both read one decision (MultigridOp::level_shape).  For
+    fine_fuse / dense_tail in {(1, T), (1, 0), (0, T)}, with the zero-guess fold on
+    and off: fine_launch(which) is true iff the level-0 plan names that launch, and
+    launch 1 on the cycle's own level-1 v reproduces the cycle's result bitwise.
+    64^3, T = 4096: the dense tail sits at level 2 and the cycle takes both launches.
+    32 x 32 x 8 (8192, 1024, 128, 16 rows), T = 4096: level 1 is the dense tail, but
+    A_0 is below the 65536 rows of DIA storage, so nothing fuses and both answers
+    are false throughout.  A fused fine level has >= 65536 rows, hence a level 1 of
+    >= 8192: 64 x 64 x 16 (65536, 8192, 1024, 128, 16 rows) with T = 8192 is the
+    smallest hierarchy whose level 1 is the dense tail under a fused level 0 -- the
+    tail's GEMV never reads d_1 f_1, so the cycle restricts with RESID0 + SET (no
+    fine-rr) and still takes fine-pj."""
+    import torch
+    A = fa().SparseMatOp.laplace3d_7pt(ctx, *dims)
+    mg = fa().sa_build_box(A, dims, (2, 2, 2), coarsest_dim=100)
+    ns = [mg.level(l)[0].nrows for l in range(mg.levels())]
+    assert len(ns) >= 4 and (ns[1] <= tail_rows) == (dims != (64, 64, 64)), ns
+    fusable, tail1 = ns[0] >= 65536, ns[1] <= tail_rows
+    b = T(np.random.default_rng(17).uniform(-1, 1, A.nrows))
+    runs = ((1, tail_rows), (1, 0), (0, tail_rows))
+    seen = {}
+    try:
+        for fold in (True, False):
+            mg.set_fold_zero_guess(fold)
+            for ff, dt in runs:
+                fa().set_flag("fine_fuse", ff)
+                fa().set_flag("dense_tail", dt)
+                z, z2 = torch.full_like(b, np.nan), torch.full_like(b, np.nan)
+                mg.apply(z, b)
+                ctx.synchronize()
+                got_pj = mg.fine_launch(1, z2, b)
+                ctx.synchronize()
+                got_rr = mg.fine_launch(0, None, b)
+                ctx.synchronize()
+                # (taken after the launches: the plan's cycle overwrites the workspace)
+                plan = mg.cycle_plan()
+                names = [p["name"] for p in plan if p["level"] == 0]
+                seen[(fold, ff, dt)] = (got_rr, got_pj)
+                print(dims, "fold", fold, "fine_fuse", ff, "dense_tail", dt, "level-0 plan", names,
+                      "fine_launch(0)", got_rr, "fine_launch(1)", got_pj)
+                assert got_pj == ("fine-pj" in names), (fold, ff, dt, names)
+                assert got_rr == ("fine-rr" in names), (fold, ff, dt, names)
+                if got_pj:
+                    assert torch.equal(z2, z), (fold, ff, dt)
+                assert (max(p["level"] for p in plan) == 1) == (dt > 0 and tail1), (dt, ns)
+    finally:
+        fa().set_flag("fine_fuse", 1)
+        fa().set_flag("dense_tail", 4096)
+        mg.set_fold_zero_guess(True)
+    # the cases are not vacuous: both launches where the cycle fuses, none with the
+    # flag or the fold off, and no fine-rr into a dense tail at level 1
+    for ff, dt in runs:
+        assert seen[(False, ff, dt)] == (False, False), seen
+        fused = fusable and ff == 1
+        assert seen[(True, ff, dt)] == (fused and not (dt > 0 and tail1), fused), seen
+
+
+@pytest.mark.parametrize("dims", [(32, 32, 32), (64, 64, 64)])
+def test_graph_cache_evicts_and_replays(ctx, dims):
+    """The hipGraph cache keeps 8 (out, rhs) pairs: ten outputs applied in turn and
+    the first again evict, re-capture and replay, every result bitwise the eager
+    cycle's; a switch (fine_fuse) drops the graphs, so the next apply into a cached
+    pair records the new launches -- still the same bits.  (At 32^3 the fine level
+    is below the 65536 rows of the fused launches, so only 64^3 has any to lose.)"""
+    import torch
+    A = fa().SparseMatOp.laplace3d_7pt(ctx, *dims)
+    mg = fa().sa_build_box(A, dims, (2, 2, 2), coarsest_dim=100)
+    b = T(np.random.default_rng(23).uniform(-1, 1, A.nrows))
+    mg.set_graph(False)
+    zref = torch.full_like(b, np.nan)
+    mg.apply(zref, b)
+    ctx.synchronize()
+    assert bool(torch.isfinite(zref).all())
+    mg.set_graph(True)
+    outs = [torch.full_like(b, np.nan) for _ in range(10)]
+    for z in outs:
+        mg.apply(z, b)
+    ctx.synchronize()
+    for i, z in enumerate(outs):
+        assert torch.equal(z, zref), i
+    for rnd in range(2):  # the first pair again: evicted above, re-captured, then replayed
+        outs[0].fill_(np.nan)
+        mg.apply(outs[0], b)
+        ctx.synchronize()
+        assert torch.equal(outs[0], zref), rnd
+    assert any(p["name"].startswith("fine-") for p in mg.cycle_plan()) == (A.nrows >= 65536)
+    fa().set_flag("fine_fuse", 0)
+    try:
+        outs[0].fill_(np.nan)
+        mg.apply(outs[0], b)
+        ctx.synchronize()
+        assert torch.equal(outs[0], zref)
+        assert not any(p["name"].startswith("fine-") for p in mg.cycle_plan())
+    finally:
+        fa().set_flag("fine_fuse", 1)
+
+
 @pytest.mark.parametrize("dims,smoother", [((64, 64, 64), "jacobi"), ((48, 40, 36), "sgs")])
 def test_dense_tail(ctx, dims, smoother):
     """The dense tail (ops.hip ensure_tail): with mu = 1 the part of the V-cycle

@@ -40,6 +40,20 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// Timing experiments only (a library built with -DFAMG_FINE_TIMING, `make TIMING=1`):
+// the environment variable FAMG_FINE_DBG, read at every launch, switches parts of
+// the fused kernels off -- the results are wrong.  The shipped library has neither
+// the variable nor the branches.
+#ifdef FAMG_FINE_TIMING
+#define FINE_DBG(a, bits) (((a).dbg & (bits)) != 0)
+#define FINE_DBG_FIELD int dbg;  // the bits of FAMG_FINE_DBG
+#define FINE_DBG_READ(a) (a).dbg = (int)env_int("FAMG_FINE_DBG", 0)
+#else
+#define FINE_DBG(a, bits) false
+#define FINE_DBG_FIELD
+#define FINE_DBG_READ(a) (void)0
+#endif
+
 typedef double dbl2_t __attribute__((ext_vector_type(2)));
 typedef double dbl2u_t __attribute__((ext_vector_type(2), aligned(8)));  // 8-B aligned 16-B loads
 
@@ -297,7 +311,7 @@ struct FineRrArgs {
     int dmode;             // 0 one value, 1 codes, 2 plain
     double dk;             // the fine level's one-value d
     double cst[7];
-    int dbg;               // timing experiments only (FAMG_FINE_DBG): 1 skips the R sums, 2 the residual
+    FINE_DBG_FIELD  // 1 skips the R sums, 2 the residual
 };
 
 // f of fine plane p at the lane's 16-B units of the window (0.0 outside the grid)
@@ -420,7 +434,7 @@ __global__ __launch_bounds__(256) void k_fine_resid_restrict(FineRrArgs a) {
         double *rp = rs + (p & 1) * FR_WPL;
 #pragma unroll
         for (int u = 0; u < FR_PP; u++) {
-            if (a.dbg & 2) break;
+            if (FINE_DBG(a, 2)) break;
             const int o = fo[u];
             const dbl2_t zm = *reinterpret_cast<const dbl2_t *>(fm + o), ym = *reinterpret_cast<const dbl2_t *>(f0 + o - FF_WX);
             const dbl2_t xc = *reinterpret_cast<const dbl2_t *>(f0 + o), yp = *reinterpret_cast<const dbl2_t *>(f0 + o + FF_WX);
@@ -447,7 +461,7 @@ __global__ __launch_bounds__(256) void k_fine_resid_restrict(FineRrArgs a) {
         fr_store(a, fgx0, fgy0, fring, p + 2, pn);            // f(p + 2): the slot of p - 2 (unread now)
         fr_fetch(a, fgx0, fgy0, min(p + 4, p1 + 1), pn);      // in flight two planes (unconditional)
         lds_barrier();
-        if (!live || (a.dbg & 1)) return;
+        if (!live || FINE_DBG(a, 1)) return;
         // the plane's terms of the two coarse chains it belongs to: chain n (coarse
         // plane Zn = (p + 1) / 2: dz = -1 at odd p, 0 at even p) and chain o (Zn - 1:
         // dz = +1, then +2 and the padding); PH = (p - p0) % 4 fixes each chain's
@@ -567,7 +581,7 @@ struct FineRr2Args {
     int dmode;  // 0 one value, 1 codes
     double dk;  // the fine level's one-value d
     double cst[7];
-    int dbg;  // timing experiments only (FAMG_FINE_DBG): 1 skips the R sums, 2 the residual
+    FINE_DBG_FIELD  // 1 skips the R sums, 2 the residual
 };
 
 struct Rr2Set {
@@ -667,7 +681,7 @@ __global__ __launch_bounds__(256, 3) void k_fine_rr(FineRr2Args a) {
         const bool pin = (unsigned)p < (unsigned)a.nz;
 #pragma unroll
         for (int u = 0; u < R2_PU; u++) {
-            if (!rin[u] || (a.dbg & 2)) continue;
+            if (!rin[u] || FINE_DBG(a, 2)) continue;
             const int q = tid + 256 * u;
             const dbl2_t ym = *reinterpret_cast<const dbl2_t *>(g0 + 2 * (q - R2_UX));
             const dbl2_t yp = *reinterpret_cast<const dbl2_t *>(g0 + 2 * (q + R2_UX));
@@ -695,7 +709,7 @@ __global__ __launch_bounds__(256, 3) void k_fine_rr(FineRr2Args a) {
             fetch_cls(Zn + 1);
         }
         lds_barrier();
-        if (!live || (a.dbg & 1)) return;
+        if (!live || FINE_DBG(a, 1)) return;
         // r(p) at the 4 x 4 positions (dy, dx) in -1..2 of the anchor (2X, 2Y): units lx, lx + 1 of rows 2 ly + dy
         double w[16];
 #pragma unroll
@@ -796,7 +810,7 @@ struct FinePj2Args {
     double *out;       // z
     double dk;
     double cst[7];
-    int dbg;  // timing experiments only (FAMG_FINE_DBG): 1 no stores, 2 no P sums, 4 no Jacobi sums
+    FINE_DBG_FIELD  // 1 no stores, 2 no P sums, 4 no Jacobi sums
 };
 
 struct Pj2Set {
@@ -883,7 +897,7 @@ __global__ __launch_bounds__(J2_NT) void k_fine_pj(FinePj2Args a) {
                 const int o0 = (int)(int16_t)(oo.x & 0xffffu), o1 = (int)(int16_t)(oo.x >> 16);
                 const int o2 = (int)(int16_t)(oo.y & 0xffffu), o3 = (int)(int16_t)(oo.y >> 16);
                 double acc = 0.0;
-                if (!(a.dbg & 2)) {
+                if (!FINE_DBG(a, 2)) {
                     acc = fma(w01.x, cring[cb[u] + o0], acc);
                     acc = fma(w01.y, cring[cb[u] + o1], acc);
                     acc = fma(w23.x, cring[cb[u] + o2], acc);
@@ -936,9 +950,9 @@ __global__ __launch_bounds__(J2_NT) void k_fine_pj(FinePj2Args a) {
         double *oz = a.out + (int64_t)min(z, a.nz - 1) * fpl;
 #pragma unroll
         for (int u = 0; u < J2_PU; u++) {
-            if (!jac[u] || !zon || (a.dbg & 1)) continue;
+            if (!jac[u] || !zon || FINE_DBG(a, 1)) continue;
             const int q = tid + J2_NT * u;
-            if (a.dbg & 4) {
+            if (FINE_DBG(a, 4)) {
                 *reinterpret_cast<dbl2_t *>(oz + off[u]) = Sz.V[u];
                 continue;
             }
@@ -1066,7 +1080,7 @@ static void fine_rr2(const GpuCsr &A, const GpuCsr &R, const double *f, double d
     }
     a.dk = dk;
     for (int k = 0; k < 7; k++) a.cst[k] = A.dia_cst_v[k];
-    a.dbg = (int)env_int("FAMG_FINE_DBG", 0);  // timing experiments only (results wrong)
+    FINE_DBG_READ(a);
     const int64_t ntxy = (int64_t)a.ntx * a.nty;
     // occupancy at a typical run length, then the run length for one round of workgroups
     const size_t dyn = (size_t)8 * R2_WS * a.nclass;
@@ -1114,7 +1128,7 @@ void fine_resid_restrict(const GpuCsr &A, const GpuCsr &R, const double *f, doub
     }
     a.dk = dk;
     for (int k = 0; k < 7; k++) a.cst[k] = A.dia_cst_v[k];
-    a.dbg = (int)env_int("FAMG_FINE_DBG", 0);  // timing experiments only (results wrong)
+    FINE_DBG_READ(a);
     const int64_t ntxy = (int64_t)a.ntx * a.nty;
     // occupancy with the dictionary part of the dynamic LDS (the per-plane class
     // bytes are small), then the run length, then the exact dynamic size
@@ -1182,7 +1196,7 @@ static void fine_pj2(const GpuCsr &A, const GpuCsr &P, const double *vc, const d
     a.out = out;
     a.dk = dk;
     for (int k = 0; k < 7; k++) a.cst[k] = A.dia_cst_v[k];
-    a.dbg = (int)env_int("FAMG_FINE_DBG", 0);  // timing experiments only (results wrong)
+    FINE_DBG_READ(a);
     const int64_t ntxy = (int64_t)a.ntx * a.nty;
     const int64_t want = (int64_t)fine_pj2_occupancy() * std::max(A.ctx ? A.ctx->num_cus : 256, 1);
     int jper = (int)std::max<int64_t>(2, ceil_div((int64_t)a.nz * ntxy, want));

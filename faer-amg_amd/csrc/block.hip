@@ -60,6 +60,108 @@ void BlockSmootherOp::apply(double *out, const double *rhs) {
     FAMG_CHECK_HIP(hipGetLastError());
 }
 
+// The k-wide apply: one workgroup per chunk of a size class and per
+// group of wc <= W columns.  The chunk's rhs entries of the group's columns go to LDS
+// with the W values of one row adjacent (sx[q * W + c]; columns wc..W-1 are zero), so
+// x_j of all columns is W / 2 16-byte reads of an address every thread of a block
+// shares (a broadcast).  The thread of block row i loads inv[j][i] once per j
+// (lane-contiguous, as k_block_apply) and feeds W chains acc_c = fma(m, x_j[c], acc_c),
+// j ascending from acc_c = 0: per column the operations of k_block_apply in their
+// order, so column c is bitwise apply() of column c.  Everything a workgroup reads of
+// r is in LDS before its first store and chunks own disjoint rows: out == r is legal.
+typedef double blk_d2 __attribute__((ext_vector_type(2)));
+
+template <int W>
+__global__ __launch_bounds__(BLK_CHUNK) void k_block_apply_cols(const int32_t *rows, const int32_t *blk_of,
+                                                                const int64_t *bptr, const int64_t *ioff,
+                                                                const int32_t *chunk, const int32_t *list,
+                                                                const double *inv, const double *r, int64_t ldr,
+                                                                double *out, int64_t ldo, int wc) {
+    extern __shared__ __align__(16) double sx[];
+    const int c = list[blockIdx.x];
+    const int p0 = chunk[c], np = chunk[c + 1] - p0;
+    for (int q = threadIdx.x; q < np; q += BLK_CHUNK) {
+        const double *rq = r + rows[p0 + q];
+        if (wc == W) {  // a full group: the W loads in flight together
+            double v[W];
+#pragma unroll
+            for (int cc = 0; cc < W; cc++) v[cc] = rq[cc * ldr];
+#pragma unroll
+            for (int cc = 0; cc < W; cc++) sx[q * W + cc] = v[cc];
+        } else {
+#pragma unroll
+            for (int cc = 0; cc < W; cc++) sx[q * W + cc] = cc < wc ? rq[cc * ldr] : 0.0;
+        }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < np; q += BLK_CHUNK) {
+        const int p = p0 + q;
+        const int b = blk_of[p];
+        const int64_t b0 = bptr[b];
+        const int s = (int)(bptr[b + 1] - b0);
+        const int i = (int)(p - b0);
+        const double *M = inv + ioff[b] + i;
+        const double *x = sx + (b0 - p0) * W;
+        double acc[W];
+#pragma unroll
+        for (int cc = 0; cc < W; cc++) acc[cc] = 0.0;
+        for (int j = 0; j < s; j++) {
+            const double m = M[(int64_t)j * s];
+            if constexpr (W == 1) {
+                acc[0] = fma(m, x[j], acc[0]);
+            } else {
+                const blk_d2 *xj = reinterpret_cast<const blk_d2 *>(x + j * W);
+#pragma unroll
+                for (int h = 0; h < W / 2; h++) {
+                    const blk_d2 t = xj[h];
+                    acc[2 * h] = fma(m, t.x, acc[2 * h]);
+                    acc[2 * h + 1] = fma(m, t.y, acc[2 * h + 1]);
+                }
+            }
+        }
+        double *oq = out + rows[p];
+#pragma unroll
+        for (int cc = 0; cc < W; cc++)
+            if (cc < wc) oq[cc * ldo] = acc[cc];
+    }
+}
+
+template <int W>
+static void launch_block_cols(BlockSmootherOp &B, int g, double *out, int64_t ldo, const double *rhs, int64_t ldr,
+                              int wc) {
+    const int64_t nch = B.cls_off[g + 1] - B.cls_off[g];
+    const size_t lds = sizeof(double) * W * (size_t)B.cls_max_rows[g];
+    // the class's inverses + rows/blk_of (8 B per row) once, r gathered + out written per column
+    log_launch("block_cols", -1, -1, B.cls_rows[g], 8 * B.cls_inv[g] + 8 * B.cls_rows[g] + 16 * B.cls_rows[g] * wc);
+    hipLaunchKernelGGL(k_block_apply_cols<W>, dim3((unsigned)nch), dim3(BLK_CHUNK), lds, B.ctx->stream, B.rows.get(),
+                       B.blk_of.get(), B.bptr.get(), B.ioff.get(), B.chunk.get(), B.cls_list.get() + B.cls_off[g],
+                       B.inv.get(), rhs, ldr, out, ldo, wc);
+    FAMG_CHECK_HIP(hipGetLastError());
+}
+
+void BlockSmootherOp::apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) {
+    if (k <= 1 || flag(FLAG_BLOCK_SMOOTHER_COLS) == 0) {
+        LinOp::apply_block(out, ldo, rhs, ldr, k);
+        return;
+    }
+    if (nchunks == 0) return;
+    FAMG_REQUIRE(ldo >= nrows && ldr >= nrows, AMG_ERR_INVALID, "block smoother apply: leading dimension too small");
+    FAMG_REQUIRE(out != rhs || ldo == ldr, AMG_ERR_INVALID, "block smoother apply: in place needs ldo == ldr");
+    for (int g = 0; g < NCLS; g++) {
+        if (cls_off[g + 1] == cls_off[g]) continue;
+        const int64_t w = CLS_W[g];
+        for (int64_t c0 = 0; c0 < k; c0 += w) {
+            const int wc = (int)std::min<int64_t>(w, k - c0);  // a short last group takes the narrowest tile
+            double *o = out + c0 * ldo;
+            const double *r = rhs + c0 * ldr;
+            if (wc > 4) launch_block_cols<8>(*this, g, o, ldo, r, ldr, wc);
+            else if (wc > 2) launch_block_cols<4>(*this, g, o, ldo, r, ldr, wc);
+            else if (wc > 1) launch_block_cols<2>(*this, g, o, ldo, r, ldr, wc);
+            else launch_block_cols<1>(*this, g, o, ldo, r, ldr, wc);
+        }
+    }
+}
+
 namespace {
 
 // dense SPD inverse (column-major in/out, s x s): Cholesky, then L^-T L^-1 e_j
@@ -262,7 +364,31 @@ std::shared_ptr<BlockSmootherOp> make_block_smoother(CsrOp &A, const int64_t *pa
     // drop empty chunks (aggregates of size 0)
     chunk.erase(std::unique(chunk.begin(), chunk.end()), chunk.end());
     op->nchunks = (int64_t)chunk.size() - 1;
+    // size classes of the k-wide apply: a chunk of more than 256 rows is one block
+    op->inv_elems = ioff[nagg];
+    std::vector<int32_t> cls_of(op->nchunks), cls_list(std::max<int64_t>(1, op->nchunks));
+    for (int64_t c = 0; c < op->nchunks; c++) {
+        const int64_t rws = chunk[c + 1] - chunk[c];
+        int g = 0;
+        while (rws > BlockSmootherOp::CLS_ROWS[g]) g++;  // rws <= BLK_MAX = CLS_ROWS[NCLS - 1]
+        cls_of[c] = g;
+        // bptr is ascending and chunk bounds are block bounds: the blocks of [chunk[c], chunk[c + 1])
+        const int64_t a0 = std::lower_bound(bptr.begin(), bptr.end(), (int64_t)chunk[c]) - bptr.begin();
+        const int64_t a1 = std::lower_bound(bptr.begin(), bptr.end(), (int64_t)chunk[c + 1]) - bptr.begin();
+        op->cls_off[g + 1]++;
+        op->cls_rows[g] += rws;
+        op->cls_inv[g] += ioff[a1] - ioff[a0];
+        op->cls_max_rows[g] = std::max(op->cls_max_rows[g], rws);
+    }
+    for (int g = 0; g < BlockSmootherOp::NCLS; g++) op->cls_off[g + 1] += op->cls_off[g];
+    {
+        int64_t at[BlockSmootherOp::NCLS];
+        std::copy(op->cls_off, op->cls_off + BlockSmootherOp::NCLS, at);
+        for (int64_t c = 0; c < op->nchunks; c++) cls_list[at[cls_of[c]]++] = (int32_t)c;
+    }
     hipStream_t st = A.ctx->stream;
+    op->cls_list.resize(cls_list.size());
+    FAMG_CHECK_HIP(hipMemcpyAsync(op->cls_list.get(), cls_list.data(), cls_list.size() * 4, hipMemcpyHostToDevice, st));
     op->rows.resize(std::max<int64_t>(1, n));
     op->blk_of.resize(std::max<int64_t>(1, n));
     op->bptr.resize(nagg + 1);
@@ -336,6 +462,23 @@ amg_status amg_block_smoother_to_csr(const amg_linop *bs, amg_linop **out) {
         FAMG_REQUIRE(b, AMG_ERR_INVALID, "operator is not a block smoother");
         b->ctx->set_device();
         *out = new amg_linop{block_smoother_to_csr(*b)};
+    });
+}
+
+amg_status amg_block_smoother_info(const amg_linop *bs, int64_t out[8]) {
+    return guard([&] {
+        FAMG_REQUIRE(bs && bs->op && out, AMG_ERR_INVALID, "bad argument");
+        auto b = std::dynamic_pointer_cast<BlockSmootherOp>(bs->op);
+        FAMG_REQUIRE(b, AMG_ERR_INVALID, "operator is not a block smoother");
+        out[0] = b->nblocks;
+        out[1] = b->max_block;
+        out[2] = b->nchunks;
+        out[3] = 8 * b->inv_elems;
+        for (int w = 0; w < 4; w++) out[4 + w] = 0;
+        for (int g = 0; g < BlockSmootherOp::NCLS; g++) {
+            const int w = BlockSmootherOp::CLS_W[g];  // 8 / 4 / 2 / 1 -> out[4..7]
+            out[w == 8 ? 4 : w == 4 ? 5 : w == 2 ? 6 : 7] += b->cls_off[g + 1] - b->cls_off[g];
+        }
     });
 }
 

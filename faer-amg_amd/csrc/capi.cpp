@@ -114,7 +114,8 @@ static std::atomic<int64_t> g_flag_val[FLAG_COUNT] = {
     {env_int("FAMG_DIA7_RP", 0)},
     {env_int("FAMG_FINE_FUSE", 1)},
     {env_int("FAMG_DENSE_TAIL", 4096)},
-    {env_int("FAMG_BLOCK_CYCLE", 1)}};
+    {env_int("FAMG_BLOCK_CYCLE", 1)},
+    {env_int("FAMG_BLOCK_SMOOTHER_COLS", 1)}};
 static std::atomic<uint64_t> g_flag_gen{0};
 int64_t flag(FlagId f) { return g_flag_val[f].load(std::memory_order_relaxed); }
 void set_flag(FlagId f, int64_t v) {

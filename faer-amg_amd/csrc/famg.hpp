@@ -986,9 +986,22 @@ struct BlockSmootherOp : LinOp {
     DevBuf<int64_t> ioff;          // nblocks+1 offsets of the inverses
     DevBuf<int32_t> chunk;         // nchunks+1 position bounds (block aligned)
     DevBuf<double> inv;
+    // k-wide apply: the chunks by size class, each class with the
+    // column width W its LDS tile (8 * rows * W bytes <= 64 KB) admits, decided at setup
+    static constexpr int NCLS = 5;
+    static constexpr int CLS_ROWS[NCLS] = {256, 1024, 2048, 4096, 8192};  // chunk rows <= this
+    static constexpr int CLS_W[NCLS] = {8, 8, 4, 2, 1};
+    int64_t inv_elems = 0;             // sum of s_b^2
+    int64_t cls_off[NCLS + 1] = {};    // class c owns cls_list[cls_off[c] .. cls_off[c + 1])
+    int64_t cls_rows[NCLS] = {}, cls_inv[NCLS] = {}, cls_max_rows[NCLS] = {};
+    DevBuf<int32_t> cls_list;          // chunk ids, class by class
     Kind kind() const override { return Kind::Block; }
     bool is_precond() const override { return true; }
     void apply(double *out, const double *rhs) override;
+    // each class once per group of up to W columns, the inverses read once per group
+    // (FLAG_BLOCK_SMOOTHER_COLS; 0 or k = 1: apply() per column); out == rhs with
+    // ldo == ldr is legal
+    void apply_block(double *out, int64_t ldo, const double *rhs, int64_t ldr, int64_t k) override;
     void apply_in_place(double *rhs) override { apply(rhs, rhs); }
 };
 // BlockSmoother (block_smoothers.rs:80-291) over a node partition (ids 0..nagg-1,

@@ -843,8 +843,9 @@ void MultigridOp::ensure_block_workspace(int64_t kw) {
 }
 
 // smooth() on a block: Jacobi ping-pongs between (V, ldv) and (T, ldt); Chebyshev is
-// k-wide (ChebyOp::apply_block); SGS and every other smoother run per column on V
-// (their level's A k-wide where they need it)
+// k-wide (ChebyOp::apply_block), and so is the BlockSmoother (in place on the residual
+// block); SGS and every other smoother run per column on V (their level's A k-wide
+// where they need it)
 void MultigridOp::block_smooth(int64_t l, double *&V, int64_t &ldv, double *&T, int64_t &ldt, const double *F,
                                int64_t ldf, int64_t kw, bool v_zero) {
     MgLevel &L = levels[l];
@@ -886,7 +887,10 @@ void MultigridOp::block_smooth(int64_t l, double *&V, int64_t &ldv, double *&T, 
             } else {
                 L.A->apply_block(T, ldt, V, ldv, kw);
                 vec_sub_cols(L.br.get(), n, F, ldf, T, ldt, n, kw, s);
-                for (int64_t c = 0; c < kw; c++) L.S->apply_in_place(L.br.get() + c * n);
+                if (auto *B = dynamic_cast<BlockSmootherOp *>(L.S.get()))
+                    B->apply_block(L.br.get(), n, L.br.get(), n, kw);  // in place, k-wide (block.hip)
+                else
+                    for (int64_t c = 0; c < kw; c++) L.S->apply_in_place(L.br.get() + c * n);
                 vec_add_cols(V, ldv, L.br.get(), n, n, kw, s);
             }
         }

@@ -139,6 +139,7 @@ SIGNATURES = {
     "amg_composite_create": (i32, [vp, vp, i64, P(vp)]),
     "amg_block_smoother_create": (i32, [vp, vp, i64, i64, P(vp)]),
     "amg_block_smoother_to_csr": (i32, [vp, P(vp)]),
+    "amg_block_smoother_info": (i32, [vp, P(i64)]),
     "amg_composite_push": (i32, [vp, vp]),
     "amg_composite_ncomponents": (i32, [vp, P(i64)]),
     "amg_comm_unique_id_size": (i32, []),
@@ -564,7 +565,8 @@ def csr_spmm_epilogue(A, mode, X, Y, B=None, d=None):
 
 FLAGS = {"fold_xscs": 0, "dia_dk": 1, "vec_wpr": 2, "gtx_time": 3, "sgs27_march": 4, "xs_pipe": 5, "bsr_kernel": 6,
          "bsr_long": 7,
-         "dia7_rp": 8, "fine_fuse": 9, "dense_tail": 10, "block_cycle": 11}
+         "dia7_rp": 8, "fine_fuse": 9, "dense_tail": 10, "block_cycle": 11,
+         "block_smoother_cols": 12}
 
 
 def set_flag(name, value):
@@ -820,7 +822,10 @@ class Multigrid(LinOp):
         """(A, S, R, P) handles of level l (R, P None on the coarsest)."""
         a, s, r, p = vp(), vp(), vp(), vp()
         _ck(_lib.amg_multigrid_get_level(self.h, l, C.byref(a), C.byref(s), C.byref(r), C.byref(p)))
-        return (SparseMatOp(a, self.ctx), LinOp(s, self.ctx),
+        S = LinOp(s, self.ctx)
+        if S.kind == "block":  # to_sparse() and info() of a level's BlockSmoother
+            S.__class__ = BlockSmoother
+        return (SparseMatOp(a, self.ctx), S,
                 SparseMatOp(r, self.ctx) if r.value else None,
                 SparseMatOp(p, self.ctx) if p.value else None)
 
@@ -1304,6 +1309,14 @@ class BlockSmoother(LinOp):
         h = vp()
         _ck(_lib.amg_block_smoother_to_csr(self.h, C.byref(h)))
         return SparseMatOp(h, self.ctx)
+
+    def info(self):
+        """amg_block_smoother_info: blocks, chunks, inverse bytes and the chunks per
+        column width of the k-wide apply (flag block_smoother_cols)."""
+        out = (i64 * 8)()
+        _ck(_lib.amg_block_smoother_info(self.h, out))
+        return {"nblocks": out[0], "max_block": out[1], "nchunks": out[2], "inverse_bytes": out[3],
+                "chunks_by_width": {8: out[4], 4: out[5], 2: out[6], 1: out[7]}}
 
 
 class Composite(LinOp):

@@ -156,7 +156,11 @@ amg_status amg_set_alloc_policy(int32_t policy);
  *                             1 (default) = one block V-cycle on the n x k block
  *                             (k-wide kernels, the matrices read once per 8
  *                             columns, eager launches), 0 = column by column (k
- *                             graph-replayed cycles); the same bits either way */
+ *                             graph-replayed cycles); the same bits either way
+ *   flag 12 FAMG_BLOCK_SMOOTHER_COLS k > 1 columns through a BlockSmoother: 1
+ *                             (default) = the k-wide kernel, every block inverse
+ *                             read once per group of up to 8 columns, 0 = one
+ *                             launch per column; the same bits either way */
 amg_status amg_set_flag(int32_t which, int64_t value);
 amg_status amg_get_flag(int32_t which, int64_t *value);
 /* Stencil-class storage of a CSR operator (structured Galerkin operators whose
@@ -279,8 +283,9 @@ amg_status amg_linop_dims(const amg_linop *op, int64_t *nrows, int64_t *ncols);
  * out: nrows x k (ld_out), rhs: ncols x k (ld_rhs).  k > 1: a CSR matrix runs one
  * SpMM; a multigrid or a Composite runs one block cycle (flag 11; chunks of 32
  * columns), a Chebyshev smoother its k-wide vector kernels with A read once per 8
- * columns, each column bitwise the k = 1 result; AMG_MEM_HOST blocks are staged
- * whole.  Other kinds apply column by column. */
+ * columns, a BlockSmoother its k-wide kernel with the block inverses read once
+ * per 8 columns (flag 12), each column bitwise the k = 1 result; AMG_MEM_HOST
+ * blocks are staged whole.  Other kinds apply column by column. */
 amg_status amg_linop_apply(amg_linop *op, double *out, int64_t ld_out, const double *rhs,
                            int64_t ld_rhs, int64_t k, amg_mem mem);
 /* BiLinOp::transpose_apply.  Supported for the symmetric operators (smoothers,
@@ -450,7 +455,9 @@ amg_status amg_multigrid_cycle_plan(amg_linop *mg, amg_launch_rec *recs, int64_t
  * k-wide SpMM launch ("spmm_dia", "spmm_scs", "spmm_bsr3", "spmm_sellp",
  * "spmm_sell", "spmm_xsell", "spmm_stream", "spmm_gtc") covers up to 8 columns: bytes = its matrix bytes
  * once + its vector bytes per column; storages without an SpMM kernel show one
- * single-vector record per column. */
+ * single-vector record per column.  A BlockSmoother level shows "block_cols"
+ * (flag 12): one record per chunk size class and group of up to 8 columns, bytes =
+ * the class's inverses and index once + its vector bytes per column. */
 amg_status amg_multigrid_block_plan(amg_linop *mg, int64_t k, amg_launch_rec *recs, int64_t cap, int64_t *count);
 /* One of the fine level's fused launches (no reference counterpart: the fused
  * forms of multigrid.rs:341-343 and 349-369 on a constant 7-point box
@@ -624,7 +631,8 @@ amg_status amg_thin_qr(amg_ctx *ctx, double *X, int64_t ld, int64_t n, int64_t k
  * k entries, may be NULL).  A is a CSR operator (A X is one SpMM, the matrix
  * streamed once per 8 columns); pc any preconditioning handle -- a Diag
  * (Jacobi/L1/L2) runs as one fused k-wide update, a multigrid or a Composite as
- * one block cycle (flag 11), every other kind is applied column by column. */
+ * one block cycle (flag 11), a BlockSmoother as its k-wide apply (flag 12),
+ * every other kind is applied column by column. */
 amg_status amg_smooth_vectors(amg_linop *A, amg_linop *pc, double *X, int64_t ld, int64_t k, int64_t iters,
                               double *cfs, amg_mem mem);
 /* create_weights (adaptivity.rs:434-443, examples/amg/main.rs:571-580):
@@ -689,6 +697,12 @@ amg_status amg_block_smoother_create(const amg_linop *A, const int64_t *node_par
                                      int64_t naggregates, int64_t block_size, amg_linop **out);
 /* BlockSmoother::into_sparse_mat (:122-146): the block-diagonal inverse as CSR. */
 amg_status amg_block_smoother_to_csr(const amg_linop *bs, amg_linop **out);
+/* Shape of a BlockSmoother's apply (no reference counterpart): out = {blocks,
+ * rows of the largest block, chunks (one workgroup each: whole blocks of at most
+ * 256 rows together, a larger block alone), bytes of the explicit inverses, and
+ * the chunks whose k-wide apply (flag 12) takes 8, 4, 2 and 1 columns per pass
+ * over the inverses: 8 up to 1024 rows, then 4 up to 2048, 2 up to 4096, 1}. */
+amg_status amg_block_smoother_info(const amg_linop *bs, int64_t out[8]);
 /* Composite (preconditioners/composite.rs:11-83) as a LinOp/Precond on A:
  * components c_0..c_{m-1} are applied c_{m-1},...,c_1,c_0,c_1,...,c_{m-1}
  * (2m-1 steps), each step out += c(r); r = rhs - A out, from out = 0 and
@@ -723,7 +737,8 @@ amg_status amg_pcg_solve(amg_linop *A, amg_linop *M, const double *b, double *x,
  * (amg_block_cg_solve below is the coupled form).
  * A P and B - A X run as one SpMM per 8 columns when A is a CSR matrix; M
  * through its block apply (a multigrid or a Composite: one block cycle, flag 11;
- * a Diag: one k-wide scale; other kinds column by column); alpha, beta and r.z
+ * a Diag: one k-wide scale; a BlockSmoother: its k-wide apply, flag 12; other
+ * kinds column by column); alpha, beta and r.z
  * stay on the device.  Per iteration the host reads the active columns' r.r in
  * one copy and one stream synchronise (amg_pcg_solve: three per column).  A
  * column that has stopped -- converged, or started at or below its tolerance,

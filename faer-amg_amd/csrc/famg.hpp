@@ -1050,6 +1050,84 @@ CsrPtr strength_graph_device(const CsrOp &A, const double *nn, int64_t ld, int64
 // sweep on the downloaded graph.  The same result either way.  info4 (optional) =
 // {passes run, roots, singleton roots, fell back (0/1)}
 int64_t aggregate_mis_device(const GpuCsr &G, int64_t max_passes, std::vector<int64_t> &agg_of, int64_t *info4);
+// ---- the modularity partitioner (partition_host.cpp, partition.hip)
+// PartitionerConfig (partitioners/mod.rs:249-329) + the device pass budget per matching round
+struct PartitionerConfig {
+    double cf = 8.0, pen = 1.0;
+    int64_t max_improve = 100, max_passes = 0;
+};
+// info8: {matching rounds, device passes (sum), most passes in one round, fell back
+// to the host (0/1), improvement passes, swaps accepted, smallest, largest aggregate}
+// The contracted graph between two matching rounds: vertex v of nv owns row v
+// (columns ascending, self loops kept), row sum rs[v], size[v] fine nodes;
+// node_to_v maps the n fine nodes.
+struct ModState {
+    int64_t nv = 0;
+    std::vector<int64_t> rp;
+    std::vector<int32_t> col;
+    std::vector<double> w, rs;
+    std::vector<int64_t> size, node_to_v;
+};
+// splitmix64 finaliser of (i << 32) | j: the tie-break of the edge order
+__host__ __device__ inline uint64_t mod_mix(uint64_t i, uint64_t j) {
+    uint64_t z = ((i << 32) | j) + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// edge (w, i, j) precedes edge (w2, i2, j2): larger w, then smaller mix, i, j
+__host__ __device__ inline bool mod_precedes(double w, int64_t i, int64_t j, double w2, int64_t i2, int64_t j2) {
+    if (w != w2) return w > w2;
+    const uint64_t m = mod_mix((uint64_t)i, (uint64_t)j), m2 = mod_mix((uint64_t)i2, (uint64_t)j2);
+    if (m != m2) return m < m2;
+    if (i != i2) return i < i2;
+    return j < j2;
+}
+// modularity weight of the candidate edge between vertices of sizes si, sj
+__host__ __device__ inline double mod_edge_weight(double s, double inv_total, double rsi, double rsj, int64_t si,
+                                                  int64_t sj, double cf, double pen) {
+    double w = s - (inv_total * rsi) * rsj;
+    const double t = (double)(si + sj) - cf;
+    if ((double)(si + sj) > cf) w -= pen * (t * t);
+    else w += pen * (t * t);
+    return w;
+}
+// size_cost (modularity.rs:385-389) with products for powf(4.)
+__host__ __device__ inline double mod_size_cost(int64_t s, double cf, double pen) {
+    const double d = (double)s - cf;
+    const double u = 4.0 * ((d < 0.0 ? -d : d) / cf);
+    return ((u * u) * (u * u)) * pen;
+}
+__host__ __device__ inline double mod_delta_q(double in, double out, int64_t dst, int64_t src, double cf, double pen) {
+    return (out - in) + pen * ((mod_size_cost(dst, cf, pen) + mod_size_cost(src, cf, pen)) -
+                               (mod_size_cost(dst + 1, cf, pen) + mod_size_cost(src - 1, cf, pen)));
+}
+// base row sums (negative clamped to 0) are the caller's; their total, summed in
+// ascending node order, inverted.  AMG_ERR_INVALID for a non-finite or zero total.
+double mod_inverse_total(const std::vector<double> &rs);
+// matching rounds from state S until nnodes / nv >= cf or a round finds no pair
+void mod_rounds_host(ModState &S, const PartitionerConfig &cfg, double inv_total, int64_t *info8);
+struct ModProposal {
+    int32_t node, agg;
+    double dq;
+};
+// the serial selection of one improvement pass (modularity.rs:477-504) over the
+// proposals (any order; sorted here); returns the swaps accepted and lists the
+// touched nodes / aggregates (for the device path's uploads)
+int64_t mod_select_swaps(std::vector<ModProposal> &props, const int64_t *rp, const int32_t *col,
+                         std::vector<int64_t> &agg, std::vector<int64_t> &size, std::vector<int64_t> *moved);
+// improvement passes on the host; then aggregates renumbered by smallest node
+void mod_improve_host(const StrengthGraph &G, const PartitionerConfig &cfg, std::vector<int64_t> &agg,
+                      std::vector<int64_t> &size, int64_t *info8);
+int64_t mod_renumber(std::vector<int64_t> &agg, int64_t na, int64_t *info8);
+int64_t partition_modularity(const StrengthGraph &G, const PartitionerConfig &cfg, std::vector<int64_t> &agg_of,
+                             int64_t *info8);
+int64_t partition_modularity_device(const GpuCsr &G, const PartitionerConfig &cfg, std::vector<int64_t> &agg_of,
+                                    int64_t *info8);
+PartitionerConfig mod_config_from(const amg_partitioner_config *cfg);  // validates: AMG_ERR_INVALID
+// amg_set_sa_partitioner: 0 MIS (default), 1 modularity with g_sa_part_cfg
+extern int g_sa_partitioner;
+extern PartitionerConfig g_sa_part_cfg;
 // tentative P for k candidates on nodes of bs dofs (interpolation/mod.rs:754-805)
 CsrPtr sa_tentative_block(Ctx *ctx, int64_t nnodes, int64_t bs, const int64_t *agg_of, int64_t naggs,
                           const double *nn, int64_t ld, int64_t k, int64_t cd, double *coarse_nn);

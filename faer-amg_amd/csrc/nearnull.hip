@@ -463,7 +463,7 @@ void find_near_null(const CsrPtr &A, double *X, int64_t ld, int64_t k, int64_t i
                                     hipMemcpyDeviceToDevice, s));
     auto l1 = make_l1(*A);
     smooth_vectors(*A, *l1, B.get(), n, k, iters, nullptr);
-    // :288-289 weights, strength graph, aggregates (MIS for the modularity partitioner), BlockSmoother
+    // :288-289 weights, strength graph, aggregates (MIS, or the modularity partitioner by policy), BlockSmoother
     std::vector<double> wts(k);
     create_weights(*A, B.get(), n, k, wts.data());
     std::vector<int64_t> agg;
@@ -476,7 +476,8 @@ void find_near_null(const CsrPtr &A, double *X, int64_t ld, int64_t k, int64_t i
     }
     if (Gd) {
         B.release();
-        na = aggregate_mis_device(Gd->m, 0, agg, nullptr);
+        na = g_sa_partitioner == 1 ? partition_modularity_device(Gd->m, g_sa_part_cfg, agg, nullptr)
+                                   : aggregate_mis_device(Gd->m, 0, agg, nullptr);
         Gd.reset();
     } else {
         std::vector<double> basis(n * k);
@@ -484,7 +485,7 @@ void find_near_null(const CsrPtr &A, double *X, int64_t ld, int64_t k, int64_t i
         FAMG_CHECK_HIP(hipStreamSynchronize(s));
         B.release();
         StrengthGraph G = strength_graph(*A, basis.data(), n, k, wts.data(), strength_depth, block_size);
-        na = aggregate_mis(G, agg);
+        na = g_sa_partitioner == 1 ? partition_modularity(G, g_sa_part_cfg, agg, nullptr) : aggregate_mis(G, agg);
     }
     auto blk = make_block_smoother(*A, agg.data(), na, block_size);
     // stage 2 (:290-296) from the caller's start block

@@ -7,11 +7,12 @@
 //  * strength graph        AdjacencyList::new_ls_strength_graph
 //                          (partitioners/mod.rs:337-393), block reduction
 //                          aggregate + filter_diag (:294-301, :464-497)
-//  * aggregation           stand-in for the modularity partitioner (OUT of
-//                          scope): aggregates seeded by the
-//                          reference's own maximal_independent_set
+//  * aggregation           by default aggregates seeded by the reference's
+//                          own maximal_independent_set
 //                          (partitioners/mod.rs:395-423) -- every root claims
-//                          its still-free strong neighbours
+//                          its still-free strong neighbours;
+//                          amg_set_sa_partitioner(1): its modularity
+//                          partitioner (partition_host.cpp, partition.hip)
 //  * tentative P           smoothed_aggregation (interpolation/mod.rs:754-805):
 //                          per-aggregate thin SVD of the local near-null block,
 //                          P = first `candidate_dimension` left singular
@@ -673,7 +674,8 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
         double ms[6] = {0, 0, 0, 0, 0, 0};  // strength, aggregation, tentative P, P smoothing, R + RAP, coarse near-null
         clk.lap();
         std::vector<int64_t> agg;
-        int64_t na = 0, edges = 0, minfo[4] = {0, 0, 0, 0};
+        int64_t na = 0, edges = 0, minfo[4] = {0, 0, 0, 0}, pinfo[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const bool modularity = g_sa_partitioner == 1;  // amg_set_sa_partitioner (partition_host.cpp)
         // policy 1 at depth 1: both stages on the device, the graph staying there (a
         // row beyond SG_MAX_ROW, like depth > 1, keeps the level on the host)
         CsrPtr Gd;
@@ -688,13 +690,18 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
         if (on_device) {
             edges = Gd->m.nnz;
             ms[0] = clk.lap();
-            na = aggregate_mis_device(Gd->m, 0, agg, minfo);
+            na = modularity ? partition_modularity_device(Gd->m, g_sa_part_cfg, agg, pinfo)
+                            : aggregate_mis_device(Gd->m, 0, agg, minfo);
             Gd.reset();
         } else {
             StrengthGraph G = strength_graph(*cur, nn.data(), cur_ld, k, w.data(), cfg.strength_depth, bs);
             edges = G.rp.back();
             ms[0] = clk.lap();
-            na = aggregate_mis(G, agg);
+            na = modularity ? partition_modularity(G, g_sa_part_cfg, agg, pinfo) : aggregate_mis(G, agg);
+        }
+        if (modularity) {  // the log's passes / fallback columns, whichever partitioner ran
+            minfo[0] = pinfo[1];
+            minfo[3] = pinfo[3];
         }
         ms[1] = clk.lap();
         if (na * cd >= n) break;  // no coarsening left (stall): stop here
@@ -709,13 +716,18 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
         ms[4] = clk.lap();
         nn_postprocess(*Ac, 3, cnn.data(), na * cd, k);
         ms[5] = clk.lap();
-        if (clk.on)
+        if (clk.on) {
+            char part[160] = "";
+            if (modularity)
+                snprintf(part, sizeof(part), " rounds %lld maxpasses %lld improve %lld swaps %lld",
+                         (long long)pinfo[0], (long long)pinfo[2], (long long)pinfo[4], (long long)pinfo[5]);
             fprintf(stderr,
                     "famg sa level %lld: n %lld nodes %lld aggregates %lld edges %lld device %d passes %lld fallback %lld"
-                    " ms: strength %.3f aggregation %.3f tentative %.3f smoothing %.3f rap %.3f nearnull %.3f\n",
+                    "%s ms: strength %.3f aggregation %.3f tentative %.3f smoothing %.3f rap %.3f nearnull %.3f\n",
                     (long long)(level - 1), (long long)n, (long long)nnodes, (long long)na, (long long)edges,
-                    on_device ? 1 : 0, (long long)minfo[0], (long long)minfo[3], ms[0], ms[1], ms[2], ms[3],
+                    on_device ? 1 : 0, (long long)minfo[0], (long long)minfo[3], part, ms[0], ms[1], ms[2], ms[3],
                     ms[4], ms[5]);
+        }
         if (info) info->push_back({n, bs, nnodes, na, edges});
         aggs.push_back(std::move(agg));
         naggs.push_back(na);

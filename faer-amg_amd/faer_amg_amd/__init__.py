@@ -183,6 +183,11 @@ SIGNATURES = {
     "amg_get_sa_setup": (i32, [P(i32)]),
     "amg_strength_graph_device": (i32, [vp, vp, i64, i64, vp, i64, C.c_int, P(vp)]),
     "amg_aggregate_mis_device": (i32, [vp, i64, vp, P(i64), vp]),
+    "amg_partitioner_config_default": (i32, [vp]),
+    "amg_partition_modularity": (i32, [vp, vp, vp, P(i64), vp]),
+    "amg_partition_modularity_device": (i32, [vp, vp, vp, P(i64), vp]),
+    "amg_set_sa_partitioner": (i32, [i32, vp]),
+    "amg_get_sa_partitioner": (i32, [P(i32), vp]),
     "amg_sa_tentative_block": (i32, [vp, i64, i64, vp, i64, vp, i64, i64, i64, P(vp), vp]),
     "amg_block_jacobi_smooth": (i32, [vp, vp, i64, dbl, P(vp)]),
     "amg_nn_postprocess": (i32, [vp, i64, vp, i64, i64]),
@@ -998,6 +1003,78 @@ def aggregate_mis_device(G, max_passes=0):
                                       info.ctypes.data_as(vp)))
     return agg[:G.nrows], na.value, {"passes": int(info[0]), "roots": int(info[1]), "singletons": int(info[2]),
                                      "fallback": bool(info[3])}
+
+
+class PartitionerConfig(C.Structure):
+    """amg_partitioner_config: PartitionerConfig (partitioners/mod.rs:249-329) and the
+    device pass budget of one matching round (max_passes, 0 = the default)."""
+    _fields_ = [("coarsening_factor", dbl), ("agg_size_penalty", dbl), ("max_improvement_iters", i64),
+                ("max_passes", i64)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _ck(_lib.amg_partitioner_config_default(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+_PART_INFO = ("rounds", "passes", "max_passes_in_round", "fallback", "improvement_passes", "swaps", "min_agg",
+              "max_agg")
+
+
+def _part_info(info):
+    d = {k: int(v) for k, v in zip(_PART_INFO, info)}
+    d["fallback"] = bool(d["fallback"])
+    return d
+
+
+def partition_modularity(G, **cfg):
+    """amg_partition_modularity of a strength graph (scipy CSR, ascending columns, no self
+    loops): (agg_of, naggs, info) -- aggregates of about coarsening_factor nodes, numbered
+    by smallest node.  cfg: PartitionerConfig fields.  info: rounds, passes,
+    max_passes_in_round, fallback, improvement_passes, swaps, min_agg, max_agg."""
+    G = G.tocsr()
+    n = G.shape[0]
+    c = PartitionerConfig(**cfg)
+    tmp = HostCsr(_host_csr_from_scipy(G))
+    agg = np.zeros(max(n, 1), np.int64)
+    na = i64()
+    info = np.zeros(8, np.int64)
+    _ck(_lib.amg_partition_modularity(tmp.h, C.byref(c), agg.ctypes.data_as(vp), C.byref(na),
+                                      info.ctypes.data_as(vp)))
+    return agg[:n], na.value, _part_info(info)
+
+
+def partition_modularity_device(G, **cfg):
+    """amg_partition_modularity_device of a square SparseMatOp (a strength_graph_device
+    result or an uploaded graph): exactly partition_modularity's (agg_of, naggs, info),
+    the matching rounds, contractions and swap proposals run on the device."""
+    c = PartitionerConfig(**cfg)
+    agg = np.zeros(max(G.nrows, 1), np.int64)
+    na = i64()
+    info = np.zeros(8, np.int64)
+    _ck(_lib.amg_partition_modularity_device(G.h, C.byref(c), agg.ctypes.data_as(vp), C.byref(na),
+                                             info.ctypes.data_as(vp)))
+    return agg[:G.nrows], na.value, _part_info(info)
+
+
+SA_PARTITIONER = {"mis": 0, "modularity": 1}
+
+
+def set_sa_partitioner(kind, **cfg):
+    """amg_set_sa_partitioner (process-wide): 'mis' / 0 (default) or 'modularity' / 1 with
+    PartitionerConfig fields -- what amg_sa_build, find_near_null and adaptive_build run
+    on the strength graph."""
+    c = PartitionerConfig(**cfg)
+    _ck(_lib.amg_set_sa_partitioner(SA_PARTITIONER[kind] if isinstance(kind, str) else int(kind), C.byref(c)))
+
+
+def get_sa_partitioner():
+    """(kind, PartitionerConfig) of amg_get_sa_partitioner."""
+    v = i32()
+    c = PartitionerConfig()
+    _ck(_lib.amg_get_sa_partitioner(C.byref(v), C.byref(c)))
+    return v.value, c
 
 
 def _host_csr_from_scipy(G):

@@ -528,8 +528,8 @@ amg_status amg_sa_build_box(amg_linop *A, int64_t nx, int64_t ny, int64_t nz, in
  * Hierarchy::coarsen (hierarchy.rs:190-248) with AggregationConfig /
  * smoothed_aggregation (interpolation/mod.rs:62-156, 730-836): strength graph
  * (partitioners/mod.rs:337-393, block-reduced :294-301), aggregates seeded by
- * maximal_independent_set (:395-423; stands in for the modularity partitioner,
- * DESIGN.md), tentative P from a per-aggregate thin SVD of the near-null block,
+ * maximal_independent_set (:395-423; the default -- amg_set_sa_partitioner(1)
+ * runs the reference's modularity partitioner instead), tentative P from a per-aggregate thin SVD of the near-null block,
  * P smoothing by Jacobi (block size 1) or block_jacobi (:963-1028), R = P^T,
  * A_c = R A P, coarse near-null by 3 L1 stationary steps + thin QR; the coarse
  * block size is candidate_dimension. */
@@ -609,6 +609,61 @@ amg_status amg_strength_graph_device(const amg_linop *A, const double *near_null
 amg_status amg_aggregate_mis_device(const amg_linop *graph, int64_t max_passes, int64_t *agg_of,
                                     int64_t *naggs, int64_t *info4);
 
+/* The modularity partitioner (partitioners/modularity.rs; PartitionerConfig,
+ * partitioners/mod.rs:249-329): aggregates of about coarsening_factor nodes of a
+ * node-level strength graph (square CSR, ascending columns, no self loops, not
+ * necessarily symmetric).  Partitioner::new without a starting partition and
+ * with unit node weights (:28-134), initialize_partition by pairwise matching
+ * rounds (greedy_matching :339-383 on generate_modularity_triplets :305-337,
+ * merged by pairwise_merge, mod.rs:109-126, :439-462, :508-578) while
+ * nnodes / naggs < coarsening_factor, then improve_partition (:437-510).  The
+ * orders the reference leaves to unstable sorts and HashSet iteration are pinned
+ * (DESIGN.md 17): candidate edges by weight descending, then by the splitmix64
+ * finaliser of (i << 32 | j), i, j; merged vertices numbered by ascending
+ * smallest member; equal columns of a merged row summed in member-then-stored
+ * order; a swap's destination ties to the smaller aggregate, proposals tie to the
+ * smaller node.  powf(2.0) and powf(4.) are products.  Aggregates come back
+ * numbered by their smallest node.  AMG_ERR_INVALID for coarsening_factor < 1, a
+ * negative penalty or budget, a non-square graph, a non-finite strength or
+ * strengths that sum to zero (the reference panics there). */
+typedef struct amg_partitioner_config {
+    double coarsening_factor;        /* 8.0 */
+    double agg_size_penalty;         /* 1.0 */
+    int64_t max_improvement_iters;   /* 100 */
+    int64_t max_passes;              /* device passes per matching round, 0 = default (256) */
+} amg_partitioner_config;
+amg_status amg_partitioner_config_default(amg_partitioner_config *cfg);
+/* agg_of: n host entries.  info8 (may be NULL) = {matching rounds, device passes
+ * summed, most device passes in one round, fell back to the host (0/1),
+ * improvement passes that proposed a swap, swaps accepted, smallest aggregate,
+ * largest aggregate}. */
+amg_status amg_partition_modularity(const amg_host_csr *graph, const amg_partitioner_config *cfg,
+                                    int64_t *agg_of, int64_t *naggs, int64_t *info8);
+/* The same aggregates, integer for integer, of a square CSR handle (a result of
+ * amg_strength_graph_device or a graph uploaded with amg_csr_create).  A
+ * matching round runs as locally dominant passes: every live vertex picks its
+ * first live incident edge in the pinned order, an edge picked at both ends is
+ * matched -- the serial sweep's matching (its stop after T + 1 pairs is a cut at
+ * the (T + 1)-th matched key).  Two launches per pass; the host reads the count
+ * of vertices that still picked an edge every 4 passes (AMG_ERR_INVALID if it
+ * stopped falling).  Past max_passes in one round the current graph is
+ * downloaded and the host finishes: the same result.  Contraction (scan of
+ * leader flags, merged rows sorted and summed per row) and the swap proposals
+ * (a lane per node, a wave per node above 64 entries) run on the device; the
+ * serial selection is the host's, on the downloaded proposals.  A graph with a
+ * row of more than 4096 entries goes to the host partitioner (fell back = 1). */
+amg_status amg_partition_modularity_device(const amg_linop *graph, const amg_partitioner_config *cfg,
+                                           int64_t *agg_of, int64_t *naggs, int64_t *info8);
+/* Which partitioner amg_sa_build (on every level), amg_find_near_null and through
+ * them amg_adaptive_build run on the strength graph (process-wide, like
+ * amg_set_sa_setup; amg_sa_config has no slot left): 0 the MIS aggregates
+ * (default: nothing changes anywhere), 1 the modularity partitioner with *cfg
+ * (NULL: the defaults) -- on the device where amg_set_sa_setup(1) holds and the
+ * level runs there, else on the host.  FAMG_SA_LOG lines then carry its rounds
+ * and passes.  AMG_ERR_INVALID for another kind or a bad cfg (nothing changes). */
+amg_status amg_set_sa_partitioner(int32_t kind, const amg_partitioner_config *cfg);
+amg_status amg_get_sa_partitioner(int32_t *kind, amg_partitioner_config *cfg);
+
 /* ---- near-null search (adaptivity.rs:264-390, 434-443) -------------------------
  * From a bare SPD matrix to the candidates amg_sa_build takes, on the device.
  * Blocks are column-major n x k with a leading dimension, 1 <= k <= 64
@@ -642,8 +697,8 @@ amg_status amg_create_weights(const amg_linop *A, const double *X, int64_t ld, i
 /* find_near_null (adaptivity.rs:264-305): stage 1 = amg_smooth_vectors with the L1
  * diagonal on a copy of the start block X; weights = amg_create_weights of that
  * basis; a BlockSmoother over amg_aggregate_mis(amg_strength_graph(A, basis,
- * weights, strength_depth, block_size)) (the MIS aggregates stand in for the
- * modularity partitioner, as in amg_sa_build); stage 2 = amg_smooth_vectors with
+ * weights, strength_depth, block_size)) (or over the modularity partition under
+ * amg_set_sa_partitioner(1), as in amg_sa_build); stage 2 = amg_smooth_vectors with
  * that BlockSmoother from the same start block (the reference draws a fresh random
  * block here).  X returns the stage-2 basis, cfs (host, k, may be NULL) its
  * convergence factors. */
@@ -666,8 +721,9 @@ amg_status amg_find_near_null(amg_linop *A, double *X, int64_t ld, int64_t k, in
  *     block cycle, flag 11).
  * cfs_out (host, may be NULL): (max_components - 1) rows of dim factors, row
  * m - 1 from search m.  Deviations from the reference: the same start block for
- * every search (the reference draws a new one each time); MIS aggregates in
- * place of the modularity partitioner; target_convergence and
+ * every search (the reference draws a new one each time); MIS aggregates
+ * unless amg_set_sa_partitioner(1) selects the modularity partitioner;
+ * target_convergence and
  * include_constant_first_near_null have no counterpart (the reference's build
  * reads neither).  sa.candidate_dimension must be <= dim. */
 typedef struct amg_adaptive_config {

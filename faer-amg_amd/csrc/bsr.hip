@@ -340,11 +340,6 @@ static bool bsr_disabled() {
 // their node columns up to missing entries), the blocks are >= 70 % filled and
 // it streams fewer bytes than `other_bytes` (the storage finalize chose).
 bool build_bsr(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes) {
-    m.bsr_data.release();
-    m.bsr_row0.release();
-    m.bsr_soff.release();
-    m.bsr_slices = m.bsr_steps = 0;
-    m.bsr_seg_slc.clear();
     if (g_spmv_format_policy != 0 || bsr_disabled() || m.no_bsr || m.nnz == 0) return false;
     if (m.nrows % BSR_B || m.ncols % BSR_B || m.nrows < 3 * BSR_C) return false;
     for (int64_t b : m.seg_rows)
@@ -455,28 +450,28 @@ bool build_bsr(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes) {
         for (int lane = (int)(row0[k + 1] - row0[k]); lane < BSR_C; lane++)  // empty lanes
             for (int64_t t = 0; t < w; t++) reinterpret_cast<int32_t *>(blk + t * BSR_STEP + BSR_COL)[lane] = 0;
     }
-    m.bsr_data.resize(std::max<size_t>(data.size(), 16));
-    m.bsr_row0.resize(ns + 1);
-    m.bsr_soff.resize(ns + 1);
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.bsr_data.get(), data.data(), data.size(), hipMemcpyHostToDevice, s));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.bsr_row0.get(), row0.data(), (ns + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.bsr_soff.get(), soff.data(), (ns + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    m.bsr.data.resize(std::max<size_t>(data.size(), 16));
+    m.bsr.row0.resize(ns + 1);
+    m.bsr.soff.resize(ns + 1);
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.bsr.data.get(), data.data(), data.size(), hipMemcpyHostToDevice, s));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.bsr.row0.get(), row0.data(), (ns + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.bsr.soff.get(), soff.data(), (ns + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
-    m.bsr_slices = ns;
-    m.bsr_steps = steps;
-    m.bsr_maxw = 0;
-    for (int64_t k = 0; k < ns; k++) m.bsr_maxw = std::max<int64_t>(m.bsr_maxw, soff[k + 1] - soff[k]);
-    m.bsr_seg_slc = seg_slc;
+    m.bsr.slices = ns;
+    m.bsr.steps = steps;
+    m.bsr.maxw = 0;
+    for (int64_t k = 0; k < ns; k++) m.bsr.maxw = std::max<int64_t>(m.bsr.maxw, soff[k + 1] - soff[k]);
+    m.bsr.seg_slc = seg_slc;
     return true;
 }
 
 void spmv_bsr(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
               int64_t seg) {
-    const int64_t s0 = seg < 0 ? 0 : m.bsr_seg_slc[seg];
-    const int64_t s1 = seg < 0 ? m.bsr_slices : m.bsr_seg_slc[seg + 1];
+    const int64_t s0 = seg < 0 ? 0 : m.bsr.seg_slc[seg];
+    const int64_t s1 = seg < 0 ? m.bsr.slices : m.bsr.seg_slc[seg + 1];
     if (s1 <= s0) return;
     static const int32_t jmask = env_is_one("FAMG_BSR_DIAG") ? 0 : -1;
-    BsrArgs a{m.bsr_data.get(), m.bsr_row0.get(), m.bsr_soff.get(), (int32_t)s0, (int32_t)(s1 - s0),
+    BsrArgs a{m.bsr.data.get(), m.bsr.row0.get(), m.bsr.soff.get(), (int32_t)s0, (int32_t)(s1 - s0),
               BsrEpi{x, y, epi.b, epi.d, epi.dc, epi.dt, epi.y2}, jmask};
     const dim3 grid((unsigned)ceil_div(s1 - s0, 4)), block(256);
     // T: the template arguments after the mode
@@ -490,13 +485,13 @@ void spmv_bsr(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
     default: fail(AMG_ERR_UNSUPPORTED, "block storage: unsupported SpMV epilogue"); \
     }
 #define FAMG_C ,
-    const int64_t how = m.bsr_maxw <= BSR_PCOL ? flag(FLAG_BSR_KERNEL) : 0;
+    const int64_t how = m.bsr.maxw <= BSR_PCOL ? flag(FLAG_BSR_KERNEL) : 0;
     const int64_t lg = flag(FLAG_BSR_LONG);
     // one-wave workgroups below 4096 slices (C5: 1097 -> 1165 V-cycles/s,
     // profiles/r05/ab_bsr_one_wave.txt)
     const bool one = s1 - s0 < BSR_ONE_WAVE_SLICES;  // (everywhere: neutral on C5's A_0)
     const dim3 grid1((unsigned)(s1 - s0)), block1(64);
-    if (lg >= 0 && m.bsr_steps >= lg * m.bsr_slices) {
+    if (lg >= 0 && m.bsr.steps >= lg * m.bsr.slices) {
         if (one) {
             const dim3 grid = grid1, block = block1;
             FAMG_BSR_LAUNCH(spmv_bsr3l_kernel, FAMG_C 1)

@@ -294,24 +294,24 @@ amg_status amg_csr_spmv_info(const amg_linop *op, int64_t *info8) {
         info8[0] = m.kernel;
         info8[1] = m.stream_bytes();
         info8[2] = m.index_bytes();
-        info8[3] = m.nslices;
-        info8[4] = m.sell_steps * 64;
-        info8[5] = m.sell_mode_slices[0];
-        info8[6] = m.sell_mode_slices[1];
-        info8[7] = m.sell_mode_slices[2];
+        info8[3] = m.sell.nslices;
+        info8[4] = m.sell.steps * 64;
+        info8[5] = m.sell.mode_slices[0];
+        info8[6] = m.sell.mode_slices[1];
+        info8[7] = m.sell.mode_slices[2];
         if (m.kernel == SPMV_KERNEL_XS) {  // slices with LDS indices as "u16", escape slices as "i32"
-            info8[3] = (int64_t)m.xs_desc.size();
-            info8[4] = m.xs_steps * 64;
+            info8[3] = (int64_t)m.xs.desc.size();
+            info8[4] = m.xs.steps * 64;
             info8[5] = 0;
-            info8[6] = info8[3] - m.xs_escape_slices;
-            info8[7] = m.xs_escape_slices;
+            info8[6] = info8[3] - m.xs.escape_slices;
+            info8[7] = m.xs.escape_slices;
         }
-        if (m.gtx_on) {  // the wide grid-transfer overlay (gtx.hip; served first)
+        if (m.gtx.built()) {  // the wide grid-transfer overlay (gtx.hip; served first)
             info8[0] = SPMV_KERNEL_GTC;
-            info8[1] = 2 * m.nrows + 12 * m.gtx_nent + 8 * m.gtx_nclass;
-        } else if (m.gtc_on) {  // the grid-transfer overlay (its modes; the storage above serves the rest)
+            info8[1] = m.gtx.stream_bytes(m.nrows);
+        } else if (m.gtc.built()) {  // the grid-transfer overlay (its modes; the storage above serves the rest)
             info8[0] = SPMV_KERNEL_GTC;
-            info8[1] = m.nrows + 2 * (int64_t)m.gtc_nce + 8 * (int64_t)m.gtc_ntab;
+            info8[1] = m.gtc.stream_bytes(m.nrows);
         }
     });
 }
@@ -320,18 +320,13 @@ amg_status amg_csr_value_codes(const amg_linop *op, int64_t *info2) {
     return guard([&] {
         FAMG_REQUIRE(info2, AMG_ERR_INVALID, "null argument");
         const GpuCsr &m = need_csr(op)->m;
-        if (m.kernel == SPMV_KERNEL_DIA) {
-            info2[0] = m.dia_vbits;
-            info2[1] = m.dia_ntab;
-        } else {
-            if (m.kernel == SPMV_KERNEL_SELLP) {
-                info2[0] = m.sellp_vbits;
-                info2[1] = m.sellp_ntab;
-                return;
-            }
-            const bool coded = m.kernel == SPMV_KERNEL_SELL || m.kernel == SPMV_KERNEL_VECTOR;
-            info2[0] = !coded ? 0 : m.kernel == SPMV_KERNEL_SELL ? m.sell_vbits : m.vec_vbits;
-            info2[1] = coded && info2[0] ? m.sell_ntab : 0;
+        info2[0] = info2[1] = 0;
+        switch (m.kernel) {
+        case SPMV_KERNEL_DIA: info2[0] = m.dia.vbits; info2[1] = m.dia.ntab; break;
+        case SPMV_KERNEL_SELLP: info2[0] = m.sellp.vbits; info2[1] = m.sellp.ntab; break;
+        case SPMV_KERNEL_SELL: info2[0] = m.sell.vbits; info2[1] = m.sell.ntab; break;
+        case SPMV_KERNEL_VECTOR: info2[0] = m.vec.vbits; info2[1] = m.vec.ntab; break;
+        default: break;
         }
     });
 }
@@ -340,11 +335,11 @@ amg_status amg_csr_class_info(const amg_linop *op, int64_t *info4) {
     return guard([&] {
         FAMG_REQUIRE(info4, AMG_ERR_INVALID, "null argument");
         const GpuCsr &m = need_csr(op)->m;
-        const bool on = m.has_scs();
-        info4[0] = on ? m.scs_nclass : 0;
-        info4[1] = on ? m.scs_k : 0;
-        info4[2] = on ? 8 * m.scs_ib : 0;
-        info4[3] = on ? 8 * m.scs_k * m.scs_nclass : 0;
+        const bool on = m.scs.built();
+        info4[0] = on ? m.scs.nclass : 0;
+        info4[1] = on ? m.scs.k : 0;
+        info4[2] = on ? 8 * m.scs.ib : 0;
+        info4[3] = on ? 8 * m.scs.k * m.scs.nclass : 0;
     });
 }
 
@@ -399,13 +394,13 @@ amg_status amg_csr_grid_info(const amg_linop *op, int64_t *info12) {
         for (int q = 0; q < 13; q++) info12[q] = 0;
         for (int q = 0; q < 3; q++) info12[q] = m.grid[q];
         info12[10] = m.grid_src;
-        info12[12] = m.xscs ? m.xscs_tile_src : 0;
-        info12[11] = m.gtx_on ? (m.gtx_r ? 4 : 3) : m.gtc_on ? (m.gtc_r ? 2 : 1) : 0;
-        const bool on = m.has_scs() && m.xscs;
+        info12[12] = m.scs.staged ? m.scs.xtile_src : 0;
+        info12[11] = m.gtx.built() ? (m.gtx.r ? 4 : 3) : m.gtc.built() ? (m.gtc.r ? 2 : 1) : 0;
+        const bool on = m.scs.built() && m.scs.staged;
         info12[3] = on ? 1 : 0;
         for (int q = 0; q < 3; q++) {
-            info12[4 + q] = on ? m.xscs_t[q] : 0;
-            info12[7 + q] = on ? m.xscs_r[q] : 0;
+            info12[4 + q] = on ? m.scs.xt[q] : 0;
+            info12[7 + q] = on ? m.scs.xr[q] : 0;
         }
     });
 }
@@ -421,11 +416,11 @@ amg_status amg_csr_dia_range(const amg_linop *op, int64_t *info4) {
     return guard([&] {
         FAMG_REQUIRE(info4, AMG_ERR_INVALID, "null argument");
         const GpuCsr &m = need_csr(op)->m;
-        const bool on = m.has_dia();
-        info4[0] = on ? m.dia_r0 : 0;
-        info4[1] = on ? m.dia_r1 : 0;
-        info4[2] = on ? m.dia_k : 0;
-        info4[3] = on ? m.dia_vbits : 0;
+        const bool on = m.dia.built();
+        info4[0] = on ? m.dia.r0 : 0;
+        info4[1] = on ? m.dia.r1 : 0;
+        info4[2] = on ? m.dia.k : 0;
+        info4[3] = on ? m.dia.vbits : 0;
     });
 }
 
@@ -720,11 +715,11 @@ amg_status amg_sgs_info(const amg_linop *op, int64_t *info4) {
         FAMG_REQUIRE(info4, AMG_ERR_INVALID, "null output");
         auto p = std::dynamic_pointer_cast<SgsOp>(need(op).shared_from_this());
         FAMG_REQUIRE(p, AMG_ERR_INVALID, "operator is not an SGS smoother");
-        const bool dia = p->Ap.has_dia() && p->Ap.dia_rowid;
+        const bool dia = p->Ap.dia.built() && p->Ap.dia.rowid;
         info4[0] = p->ncolors;
         info4[1] = dia ? SPMV_KERNEL_DIA : p->Ap.kernel;
-        info4[2] = dia ? p->Ap.dia_k : 0;
-        info4[3] = dia ? p->Ap.dia_vbits : 0;
+        info4[2] = dia ? p->Ap.dia.k : 0;
+        info4[3] = dia ? p->Ap.dia.vbits : 0;
     });
 }
 

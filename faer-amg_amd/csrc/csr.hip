@@ -250,6 +250,9 @@ static void infer_grid(GpuCsr &m, const std::vector<int64_t> &rp) {
 
 void csr_finalize(GpuCsr &m, const std::vector<int64_t> *segments) {
     Ctx &ctx = *m.ctx;
+    // every storage of an earlier finalize goes, with its HBM; the builds below start from defaults
+    m.sell = {}; m.dia = {}; m.vec = {}; m.bsr = {}; m.sellp = {}; m.scs = {}; m.gtc = {}; m.gtx = {}; m.xs = {};
+    m.tried_gtc = m.tried_gtx = false;
     if (segments) {
         FAMG_REQUIRE(segments->size() >= 2 && segments->front() == 0 && segments->back() == m.nrows,
                      AMG_ERR_INVALID, "row segments must start at 0 and end at nrows");
@@ -279,68 +282,28 @@ void csr_finalize(GpuCsr &m, const std::vector<int64_t> *segments) {
                                   hipMemcpyHostToDevice, ctx.stream));
     FAMG_CHECK_HIP(hipStreamSynchronize(ctx.stream));
     if (!m.order_fixed) infer_grid(m, rp);  // a renumbered copy keeps no grid (reorder.hip)
-    scs_release(m);
-    sellp_release(m);
-    gtc_release(m);
-    gtx_release(m);
-    m.gtc_tried = m.gtx_tried = false;
     build_sell(m, rp);
-    const bool dia_all = m.has_dia() && m.dia_r0 == 0 && m.dia_r1 == m.nrows;
-    const int64_t sell_b = m.sell_bytes + 12 * (m.nslices + 1) + 4 * m.sell_steps + 8 * m.sell_ntab;
-    if (!dia_all && build_bsr(m, rp, m.has_sell() ? sell_b : m.index_bytes())) {
-        // the block storage replaces the SELL copy (release its HBM)
-        m.sell_row0.release(); m.sell_soff.release(); m.sell_desc.release(); m.sell_base.release();
-        m.sell_data.release(); m.sell_vtab.release();
-        m.nslices = m.sell_steps = m.sell_bytes = m.sell_ntab = 0;
-        m.sell_vbits = 0;
-        m.sell_mode_slices[0] = m.sell_mode_slices[1] = m.sell_mode_slices[2] = 0;
-    }
+    const bool dia_all = m.dia.built() && m.dia.r0 == 0 && m.dia.r1 == m.nrows;
+    const int64_t sell_b = m.sell.stream_bytes();
+    // the block storage replaces the SELL copy
+    if (!dia_all && build_bsr(m, rp, m.sell.built() ? sell_b : m.index_bytes())) m.sell = {};
     // structured operators: stencil classes, else the pattern SELL, replace
     // SELL-64 / wave-per-row
-    const int64_t other_b = m.has_sell() ? sell_b : 10 * m.nnz + 4 * (m.nrows + 1);
+    const int64_t other_b = m.sell.built() ? sell_b : 10 * m.nnz + 4 * (m.nrows + 1);
     // long DIA run patterns (> 27 diagonals: A_1 of the 7-point box hierarchy) on a
     // grid may run faster as x-staged stencil classes: both are built and timed
-    const bool dia_vs_xscs = dia_all && m.dia_k > 27 && m.grid[0] > 0;
-    const bool scs = (!dia_all || dia_vs_xscs) && !m.has_bsr() && !m.order_fixed && build_scs(m, rp, other_b);
+    const bool dia_vs_xscs = dia_all && m.dia.k > 27 && m.grid[0] > 0;
+    const bool scs = (!dia_all || dia_vs_xscs) && !m.bsr.built() && !m.order_fixed && build_scs(m, rp, other_b);
     if (dia_vs_xscs && scs) {
-        if (m.xscs && xscs_beats_dia(m)) {
-            m.dia_codes.release();
-            m.dia_vtab.release();
-            m.dia_ntab = 0;
-            m.dia_k = m.dia_cw = m.dia_vbits = m.dia_pat = 0;
-            m.dia_r0 = m.dia_r1 = m.dia_seg = 0;
-            m.dia_off.clear();
-        } else {
-            scs_release(m);
-        }
+        if (m.scs.staged && xscs_beats_dia(m)) m.dia = {};
+        else m.scs = {};
     }
-    const bool scs_all = scs && m.scs_seg < 0;  // else a row segment beside SELL-64
-    if (scs_all && m.has_dia() && !dia_all) {  // the classes take every row: no segment DIA beside them
-        m.dia_codes.release();
-        m.dia_vtab.release();
-        m.dia_ntab = 0;
-        m.dia_k = m.dia_cw = m.dia_vbits = m.dia_pat = 0;
-        m.dia_r0 = m.dia_r1 = m.dia_seg = 0;
-        m.dia_off.clear();
-    }
-    if (!dia_all && !m.has_bsr() && (scs_all || (!scs && !m.order_fixed && build_sellp(m, rp, other_b)))) {
-        m.sell_row0.release(); m.sell_soff.release(); m.sell_desc.release(); m.sell_base.release();
-        m.sell_data.release(); m.sell_vtab.release();
-        m.nslices = m.sell_steps = m.sell_bytes = m.sell_ntab = 0;
-        m.sell_vbits = 0;
-        m.sell_mode_slices[0] = m.sell_mode_slices[1] = m.sell_mode_slices[2] = 0;
-    }
+    const bool scs_all = scs && m.scs.seg < 0;  // else a row segment beside SELL-64
+    if (scs_all && m.dia.built() && !dia_all) m.dia = {};  // the classes take every row: no segment DIA beside them
+    if (!dia_all && !m.bsr.built() && (scs_all || (!scs && !m.order_fixed && build_sellp(m, rp, other_b)))) m.sell = {};
     // gather-heavy fp64 SELL: x staged in LDS per row group (replaces SELL-64)
-    xs_release(m);
-    if (!dia_all && !m.has_bsr() && !m.has_sellp() && !m.has_scs() && build_xs(m, rp)) {
-        m.sell_row0.release(); m.sell_soff.release(); m.sell_desc.release(); m.sell_base.release();
-        m.sell_data.release(); m.sell_vtab.release();
-        m.nslices = m.sell_steps = m.sell_bytes = m.sell_ntab = 0;
-        m.sell_vbits = 0;
-        m.sell_mode_slices[0] = m.sell_mode_slices[1] = m.sell_mode_slices[2] = 0;
-    }
+    if (!dia_all && !m.bsr.built() && !m.sellp.built() && !m.scs.built() && build_xs(m, rp)) m.sell = {};
     choose_kernel(m);
-    m.dia_cst = false;
     if (m.kernel == SPMV_KERNEL_DIA) dia_constant(m);
     if (storage_check_enabled()) storage_check(m);
 }

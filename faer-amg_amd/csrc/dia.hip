@@ -745,24 +745,24 @@ bool build_dia(GpuCsr &m, int vb, const std::vector<unsigned long long> &tab, co
     for (int k = 0; k < K; k++) oa.off[k] = offs[k];
     const int zero_code = (int)(std::lower_bound(tab.begin(), tab.end(), 0ull) - tab.begin());
     const int64_t nalloc = nr + 2;
-    m.dia_codes.resize(nalloc * cw);
-    m.dia_vtab.resize(tab.size());
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.dia_vtab.get(), tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    m.dia.codes.resize(nalloc * cw);
+    m.dia.vtab.resize(tab.size());
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.dia.vtab.get(), tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_dia_fill, dim3((unsigned)ceil_div(nalloc, 256)), dim3(256), 0, s, m.rp64.get(), m.col.get(),
                        m.val.get(), r0, r1, nalloc, rowid, oa, vb, cw,
-                       reinterpret_cast<const unsigned long long *>(m.dia_vtab.get()), (int)tab.size(), zero_code,
-                       m.dia_codes.get());
+                       reinterpret_cast<const unsigned long long *>(m.dia.vtab.get()), (int)tab.size(), zero_code,
+                       m.dia.codes.get());
     FAMG_CHECK_HIP(hipGetLastError());
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
-    m.dia_k = K;
-    m.dia_cw = cw;
-    m.dia_off = offs;
-    m.dia_r0 = r0;
-    m.dia_r1 = r1;
-    m.dia_vbits = vb;
-    m.dia_ntab = (int64_t)tab.size();
-    m.dia_rowid = rowid;
-    m.dia_pat = pat;
+    m.dia.k = K;
+    m.dia.cw = cw;
+    m.dia.off = offs;
+    m.dia.r0 = r0;
+    m.dia.r1 = r1;
+    m.dia.vbits = vb;
+    m.dia.ntab = (int64_t)tab.size();
+    m.dia.rowid = rowid;
+    m.dia.pat = pat;
     return true;
 }
 
@@ -777,15 +777,12 @@ bool build_dia_sgs(GpuCsr &m, const int32_t *rowid) {
     FAMG_CHECK_HIP(hipStreamSynchronize(m.ctx->stream));
     std::vector<unsigned long long> tab;
     const int vb = csr_value_table(m, tab);
-    DevBuf<uint32_t> keep_codes = std::move(m.dia_codes);  // a segment DIA the finalize may have built
-    DevBuf<double> keep_tab = std::move(m.dia_vtab);
+    DiaStore keep = std::move(m.dia);  // a segment DIA the finalize may have built
     if (!build_dia(m, vb, tab, rp, 0, m.nrows, rowid)) {
-        m.dia_codes = std::move(keep_codes);
-        m.dia_vtab = std::move(keep_tab);
-        m.dia_rowid = nullptr;
+        m.dia = std::move(keep);
         return false;
     }
-    m.dia_seg = -2;  // not a row segment of the plain SpMV
+    m.dia.seg = -2;  // not a row segment of the plain SpMV
     return true;
 }
 
@@ -839,23 +836,23 @@ static void launch_dia(int runs, bool nt, dim3 grid, dim3 block, hipStream_t s, 
 // The 27-point run pattern (nine runs of three consecutive offsets) and the
 // 7-point one (single, single, run of three, single, single) of the DIA kernels
 static bool dia_run9(const GpuCsr &m) {
-    bool runs9 = m.dia_k == 27 && dia_runs();
+    bool runs9 = m.dia.k == 27 && dia_runs();
     for (int j = 0; runs9 && j < 9; j++)
-        runs9 = m.dia_off[3 * j + 1] == m.dia_off[3 * j] + 1 && m.dia_off[3 * j + 2] == m.dia_off[3 * j] + 2;
+        runs9 = m.dia.off[3 * j + 1] == m.dia.off[3 * j] + 1 && m.dia.off[3 * j + 2] == m.dia.off[3 * j] + 2;
     return runs9;
 }
 static bool dia_run7(const GpuCsr &m) {
-    return m.dia_k == 7 && dia_runs7() && m.dia_off[3] == m.dia_off[2] + 1 && m.dia_off[4] == m.dia_off[2] + 2;
+    return m.dia.k == 7 && dia_runs7() && m.dia.off[3] == m.dia.off[2] + 1 && m.dia.off[4] == m.dia.off[2] + 2;
 }
 
 // JACOBI / RESID0 with a coded diagonal of one value on the 7-point DIA kernel:
 // d is dt[0], no codes are read
-static bool dia_dk(const GpuCsr &m, const SpmvEpi &epi) { return epi_dconst(epi) && !m.dia_pat && dia_run7(m); }
+static bool dia_dk(const GpuCsr &m, const SpmvEpi &epi) { return epi_dconst(epi) && !m.dia.pat && dia_run7(m); }
 
 bool dia7_cst_dk(const GpuCsr &m, const SpmvEpi &epi) {
-    return m.kernel == SPMV_KERNEL_DIA && m.dia_cst && m.dia_k == 7 && dia_cst_enabled() && dia_dk(m, epi) &&
-           m.dia_vbits > 0 && m.dia_cw * 32 / m.dia_vbits >= 7 &&
-           m.nrows == (int64_t)m.dia_cst_n[0] * m.dia_cst_n[1] * m.dia_cst_n[2];
+    return m.kernel == SPMV_KERNEL_DIA && m.dia.cst && m.dia.k == 7 && dia_cst_enabled() && dia_dk(m, epi) &&
+           m.dia.vbits > 0 && m.dia.cw * 32 / m.dia.vbits >= 7 &&
+           m.nrows == (int64_t)m.dia.cst_n[0] * m.dia.cst_n[1] * m.dia.cst_n[2];
 }
 
 // The DIA part of a route (spmv_route chose ROUTE_DIA or ROUTE_DIA_SGS): which of
@@ -867,9 +864,9 @@ void dia_route(const GpuCsr &m, const SpmvEpi &epi, SpmvRoute &r) {
         r.name = "dia_sgs";
         return;
     }
-    const int key = m.dia_vbits * 16 + m.dia_cw;
-    r.pat = m.dia_pat ? m.dia_pat : r.runs == 9 && dia_pat27() && (key == 4 * 16 + 4 || key == 8 * 16 + 8) ? 27 : 0;
-    r.cst = m.dia_cst && r.seg < 0 && dia_cst_enabled() && (r.pat ? r.pat == 27 : r.runs == -1 && m.dia_k == 7);
+    const int key = m.dia.vbits * 16 + m.dia.cw;
+    r.pat = m.dia.pat ? m.dia.pat : r.runs == 9 && dia_pat27() && (key == 4 * 16 + 4 || key == 8 * 16 + 8) ? 27 : 0;
+    r.cst = m.dia.cst && r.seg < 0 && dia_cst_enabled() && (r.pat ? r.pat == 27 : r.runs == -1 && m.dia.k == 7);
     r.dk = dia_dk(m, epi);
     r.rc = epi.dc && dia_rc_enabled();
     r.name = r.pat ? "dia_pat" : "dia";
@@ -878,21 +875,21 @@ void dia_route(const GpuCsr &m, const SpmvEpi &epi, SpmvRoute &r) {
 // The arguments every DIA launch shares: rows [r.r0, r.r1) of m
 static DiaArgs dia_args(const GpuCsr &m, const double *x, double *y, const SpmvEpi &epi, const SpmvRoute &r) {
     DiaArgs a{};
-    a.codes = m.dia_codes.get();
-    a.ntab = (int32_t)m.dia_ntab;
-    a.k = m.dia_k;
+    a.codes = m.dia.codes.get();
+    a.ntab = (int32_t)m.dia.ntab;
+    a.k = m.dia.k;
     a.row_begin = (int32_t)r.r0;
     a.row_end = (int32_t)r.r1;
     a.ncols = (int32_t)m.ncols;
-    a.code_row0 = (int32_t)m.dia_r0;
-    a.vtab = m.dia_vtab.get();
-    for (int k = 0; k < m.dia_k; k++) a.off[k] = m.dia_off[k];
+    a.code_row0 = (int32_t)m.dia.r0;
+    a.vtab = m.dia.vtab.get();
+    for (int k = 0; k < m.dia.k; k++) a.off[k] = m.dia.off[k];
     a.e = Epi{x, y, epi.b, epi.d, epi.perm, epi.dc, epi.dt, epi.dk};
     if (r.cst) {
-        a.gnx = m.dia_cst_n[0];
-        a.gny = m.dia_cst_n[1];
-        a.gnz = m.dia_cst_n[2];
-        for (int k = 0; k < m.dia_k; k++) a.cst[k] = m.dia_cst_v[k];
+        a.gnx = m.dia.cst_n[0];
+        a.gny = m.dia.cst_n[1];
+        a.gnz = m.dia.cst_n[2];
+        for (int k = 0; k < m.dia.k; k++) a.cst[k] = m.dia.cst_v[k];
     }
     return a;
 }
@@ -900,24 +897,24 @@ static DiaArgs dia_args(const GpuCsr &m, const double *x, double *y, const SpmvE
 // One color sweep of a color-permuted copy
 void spmv_dia_sgs(const GpuCsr &m, const double *x, double *y, const SpmvEpi &epi, hipStream_t s,
                   const SpmvRoute &r) {
-    FAMG_REQUIRE(epi.perm == m.dia_rowid, AMG_ERR_INVALID, "SGS DIA: permutation mismatch");
+    FAMG_REQUIRE(epi.perm == m.dia.rowid, AMG_ERR_INVALID, "SGS DIA: permutation mismatch");
     if (r.r1 <= r.r0) return;
     const DiaArgs a = dia_args(m, x, y, epi, r);
     const dim3 grid((unsigned)ceil_div(r.r1 - r.r0, 256)), block(256);
-    const int key = m.dia_vbits * 16 + m.dia_cw;
+    const int key = m.dia.vbits * 16 + m.dia.cw;
     if (r.runs == 9 && key == 4 * 16 + 4) {
-        spmv_dia_sgs_kernel<4, 4, 9><<<grid, block, 0, s>>>(a, m.dia_rowid);
+        spmv_dia_sgs_kernel<4, 4, 9><<<grid, block, 0, s>>>(a, m.dia.rowid);
     } else if (r.runs == 9 && key == 8 * 16 + 8) {
-        spmv_dia_sgs_kernel<8, 8, 9><<<grid, block, 0, s>>>(a, m.dia_rowid);
+        spmv_dia_sgs_kernel<8, 8, 9><<<grid, block, 0, s>>>(a, m.dia.rowid);
     } else {
         switch (key) {
-        case 4 * 16 + 1: spmv_dia_sgs_kernel<4, 1><<<grid, block, 0, s>>>(a, m.dia_rowid); break;
-        case 4 * 16 + 2: spmv_dia_sgs_kernel<4, 2><<<grid, block, 0, s>>>(a, m.dia_rowid); break;
-        case 4 * 16 + 4: spmv_dia_sgs_kernel<4, 4><<<grid, block, 0, s>>>(a, m.dia_rowid); break;
-        case 8 * 16 + 1: spmv_dia_sgs_kernel<8, 1><<<grid, block, 0, s>>>(a, m.dia_rowid); break;
-        case 8 * 16 + 2: spmv_dia_sgs_kernel<8, 2><<<grid, block, 0, s>>>(a, m.dia_rowid); break;
-        case 8 * 16 + 4: spmv_dia_sgs_kernel<8, 4><<<grid, block, 0, s>>>(a, m.dia_rowid); break;
-        case 8 * 16 + 8: spmv_dia_sgs_kernel<8, 8><<<grid, block, 0, s>>>(a, m.dia_rowid); break;
+        case 4 * 16 + 1: spmv_dia_sgs_kernel<4, 1><<<grid, block, 0, s>>>(a, m.dia.rowid); break;
+        case 4 * 16 + 2: spmv_dia_sgs_kernel<4, 2><<<grid, block, 0, s>>>(a, m.dia.rowid); break;
+        case 4 * 16 + 4: spmv_dia_sgs_kernel<4, 4><<<grid, block, 0, s>>>(a, m.dia.rowid); break;
+        case 8 * 16 + 1: spmv_dia_sgs_kernel<8, 1><<<grid, block, 0, s>>>(a, m.dia.rowid); break;
+        case 8 * 16 + 2: spmv_dia_sgs_kernel<8, 2><<<grid, block, 0, s>>>(a, m.dia.rowid); break;
+        case 8 * 16 + 4: spmv_dia_sgs_kernel<8, 4><<<grid, block, 0, s>>>(a, m.dia.rowid); break;
+        case 8 * 16 + 8: spmv_dia_sgs_kernel<8, 8><<<grid, block, 0, s>>>(a, m.dia.rowid); break;
         default: fail(AMG_ERR_INVALID, "SGS DIA: unsupported code layout");
         }
     }
@@ -931,12 +928,12 @@ void spmv_dia(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
     if (r.r1 <= r.r0) return;
     DiaArgs a = dia_args(m, x, y, epi, r);
     {  // plane = the largest diagonal offset (a 3-D stencil's z neighbour)
-        const int64_t plane = std::max<int64_t>(std::abs((int64_t)m.dia_off.front()), std::abs((int64_t)m.dia_off.back()));
+        const int64_t plane = std::max<int64_t>(std::abs((int64_t)m.dia.off.front()), std::abs((int64_t)m.dia.off.back()));
         if (dia_bands() && plane % 4096 == 0 && plane >= 8 * 4096 && (r.r1 - r.r0) % plane == 0)
             a.band_bp = (int32_t)(plane / 512);
     }
     const dim3 grid((unsigned)ceil_div(r.r1 - r.r0, 512)), block(256);
-    const int key = m.dia_vbits * 16 + m.dia_cw;
+    const int key = m.dia.vbits * 16 + m.dia.cw;
     if (r.pat) {
 #define FAMG_DIAP2(M, VB, CW, P)                                                                  \
     if (r.cst) spmv_dia_pat_kernel<M, VB, CW, P, (P == 27)><<<grid, block, 0, s>>>(a);            \

@@ -1146,9 +1146,9 @@ static std::shared_ptr<DistMultigridOp> build_dist(amg_comm *comm, MultigridOp &
         {
             auto *Ag = dynamic_cast<CsrOp *>(g.levels[l].A.get());
             auto *Rg = dynamic_cast<CsrOp *>(g.levels[l].R.get());
-            d->L[l].A->m.vec_wpr = Ag->m.vec_wpr;
-            d->L[l].R->m.vec_wpr = Rg->m.vec_wpr;
-            if (l > 0) d->L[l - 1].P->m.vec_wpr = dynamic_cast<CsrOp *>(g.levels[l - 1].P.get())->m.vec_wpr;
+            d->L[l].A->m.vec.wpr = Ag->m.vec.wpr;
+            d->L[l].R->m.vec.wpr = Rg->m.vec.wpr;
+            if (l > 0) d->L[l - 1].P->m.vec.wpr = dynamic_cast<CsrOp *>(g.levels[l - 1].P.get())->m.vec.wpr;
         }
         for (auto *op : {d->L[l].A.get(), d->L[l].R.get()}) {
             op->nrows = op->m.nrows;
@@ -1173,7 +1173,7 @@ static std::shared_ptr<DistMultigridOp> build_dist(amg_comm *comm, MultigridOp &
         set_frames(D.P->m, D.sp.frame, owned_frame(Ag, 0, Ag.nrows), false);
         csr_finalize(D.P->m);
         // the same waves per row as the global P (finalize chose from the local rows)
-        D.P->m.vec_wpr = dynamic_cast<CsrOp *>(g.levels[d->La - 1].P.get())->m.vec_wpr;
+        D.P->m.vec.wpr = dynamic_cast<CsrOp *>(g.levels[d->La - 1].P.get())->m.vec.wpr;
     }
     // R_l / P_l of a 2x2x2-box level as grid-transfer classes through the slab
     // frames (the classes of their global rows; every entry checked)
@@ -1186,8 +1186,8 @@ static std::shared_ptr<DistMultigridOp> build_dist(amg_comm *comm, MultigridOp &
         GpuCsr &R = d->L[l].R->m, &Pm = d->L[l].P->m;
         if (R.nrows > 0) gtc_attach(R, Af.grid, Ac.grid, 1);  // gtc_classes checks the frames / grids first
         if (Pm.nrows > 0) gtc_attach(Pm, Af.grid, Ac.grid, 0);
-        if (R.nrows > 0 && (!R.gtc_on || gtx_mode() == 2)) gtx_attach(R, Af.grid, Ac.grid, 1);
-        if (Pm.nrows > 0 && (!Pm.gtc_on || gtx_mode() == 2)) gtx_attach(Pm, Af.grid, Ac.grid, 0);
+        if (R.nrows > 0 && (!R.gtc.built() || gtx_mode() == 2)) gtx_attach(R, Af.grid, Ac.grid, 1);
+        if (Pm.nrows > 0 && (!Pm.gtc.built() || gtx_mode() == 2)) gtx_attach(Pm, Af.grid, Ac.grid, 0);
     }
     for (int64_t l = 0; l < d->La; l++) {
         d->L[l].P->nrows = d->L[l].P->m.nrows;

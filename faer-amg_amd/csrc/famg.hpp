@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "gpu_csr.hpp"
 
 namespace famg {
 
@@ -48,208 +49,7 @@ inline bool fdiv_exact(int n, int d, float r) {
 }
 
 // ------------------------------------------------------------------ CSR data
-
-// Plane layout of a rank-local vector of a distributed grid level (dist.hip,
-// DESIGN.md 6): the rank owns planes [z0, z0 + nz) of an nx x ny x gz grid
-// (local entries [0, nz * pl)), then its ghost planes -- gl whole planes below z0,
-// then gh above z0 + nz.  Local plane z in [-gl, nz + gh) starts at entry
-// z * pl + (z < 0 ? nz * pl + gl * pl : z >= nz ? gl * pl : 0).
-// Off (nx == 0) for single-GPU matrices; a redundant (all-gathered) level is
-// the frame with z0 = 0, nz = gz and no ghosts.
-struct SlabFrame {
-    int64_t nx = 0, ny = 0, gz = 0;  // the global grid
-    int64_t z0 = 0, nz = 0;          // owned planes
-    int64_t gl = 0, gh = 0;          // ghost planes below / above
-    bool on() const { return nx > 0; }
-    int64_t pl() const { return nx * ny; }
-    int64_t n_own() const { return nz * nx * ny; }
-    int64_t add_lo() const { return (nz + gl) * nx * ny; }  // added to z * pl for z < 0
-    int64_t add_hi() const { return gl * nx * ny; }         // ... for z >= nz
-    // global grid plane of a local entry (ghosts included)
-    int64_t plane_of(int64_t c) const {
-        const int64_t p = pl(), own = n_own();
-        if (c < own) return z0 + c / p;
-        const int64_t g = c - own;
-        return g < gl * p ? z0 - gl + g / p : z0 + nz + (g - gl * p) / p;
-    }
-    int64_t in_plane(int64_t c) const {
-        const int64_t p = pl(), own = n_own();
-        return c < own ? c % p : (c - own) % p;
-    }
-};
-
-// A CSR matrix resident on the device.  rp64 (int64 row pointers) always
-// exists and is what setup kernels (SpGEMM, transpose, extraction) read;
-// rp32 + the stream schedule exist when nnz < 2^31 and are what SpMV reads
-// (12 B per entry + 4 B per row of index/value traffic).
-struct GpuCsr {
-    Ctx *ctx = nullptr;
-    int64_t nrows = 0, ncols = 0, nnz = 0;
-    DevBuf<int64_t> rp64;
-    DevBuf<int32_t> rp32;
-    DevBuf<int32_t> col;   // padded by 4 entries (16-B vector loads)
-    DevBuf<double> val;    // padded by 2 entries
-    DevBuf<int32_t> sched; // stream-SpMV row blocks: nblocks+1 row starts
-    int64_t nblocks = 0;
-    // Row segments (SGS colors, halo boundary/interior): [seg_rows[g], seg_rows[g+1]).
-    // Schedule blocks and SELL slices never straddle a segment.
-    std::vector<int64_t> seg_rows, seg_blk, seg_slc;
-    // SELL-64 copy with compressed column indices (sell.hip):
-    // slice s holds rows [sell_row0[s], sell_row0[s+1]) (<= 64), one lane per
-    // row, sell_soff[s+1]-sell_soff[s] entry steps; sell_desc[s] = byte offset/128
-    // of its block in sell_data | column mode << 30; sell_base = one int32 per step.
-    DevBuf<int32_t> sell_row0;
-    DevBuf<int32_t> sell_soff;
-    DevBuf<uint32_t> sell_desc;
-    DevBuf<int32_t> sell_base;
-    DevBuf<char> sell_data;
-    int64_t nslices = 0, sell_steps = 0, sell_bytes = 0;
-    int64_t sell_mode_slices[3] = {0, 0, 0};  // slices per column mode (implicit, u16, i32)
-    bool sell_paired = true;  // step-pair layout (16-B value loads); false: one step per 512-B row
-    bool sell_short = false;  // coded slices of <= 4 steps in equal pairs (spmv_sell_short_kernel)
-    // value codes (sell.hip "value codes"): 0 = fp64 values, else 4/8/16-bit codes
-    // into sell_vtab (sell_ntab distinct bit patterns, ascending)
-    int sell_vbits = 0;
-    int64_t sell_ntab = 0;
-    DevBuf<double> sell_vtab;
-    // DIA codes (dia.hip): dia_cw words of codes per row for the
-    // dia_k diagonals dia_off (ascending); value table = sell_vtab
-    DevBuf<uint32_t> dia_codes;
-    DevBuf<double> dia_vtab;
-    int64_t dia_ntab = 0;
-    int dia_k = 0, dia_cw = 0, dia_vbits = 0;
-    int dia_pat = 0;  // > 32 diagonals: the run pattern (spmv_dia_pat_kernel)
-    // 7- or 27-point DIA operator whose every row is the interior stencil truncated
-    // at the grid faces (dia_constant): the kernels read no codes
-    bool dia_cst = false;
-    int dia_cst_n[3] = {0, 0, 0};
-    double dia_cst_v[27] = {0};
-    std::vector<int> dia_off;
-    // DIA row range: the whole matrix (kernel == DIA) or one row segment
-    // (dia_seg, e.g. the halo interior of a distributed level) beside SELL
-    int64_t dia_r0 = 0, dia_r1 = 0, dia_seg = 0;
-    // set when the DIA codes describe a color-permuted SGS copy: stored row p
-    // is original row dia_rowid[p] (device array owned by the SgsOp)
-    const int32_t *dia_rowid = nullptr;
-    // wave-per-row storage compression: 8/16-bit value codes (vec_codes, table
-    // sell_vtab) and 16-bit column offsets from the row (vec_off)
-    DevBuf<uint8_t> vec_codes;
-    DevBuf<int16_t> vec_off;
-    int vec_vbits = 0;
-    bool vec_o16 = false;
-    int vec_wpr = 1;  // waves per row, chosen once for the whole matrix (flag FLAG_VEC_WPR overrides)
-    // 3x3 block storage (bsr.hip): node-row slices, one 4864-B unit per block step
-    DevBuf<char> bsr_data;
-    DevBuf<int32_t> bsr_row0, bsr_soff;
-    int64_t bsr_slices = 0, bsr_steps = 0, bsr_maxw = 0;
-    std::vector<int64_t> bsr_seg_slc;
-    bool no_bsr = false;  // e.g. a color-permuted SGS copy
-    bool bsr_pin = false;  // a renumbered copy of a 3x3-block matrix: take the block storage whenever it builds
-    int8_t kind_pin = -1;  // a renumbered copy: 0 one-lane storages (SELL / x-staged) whenever they build, 1 wave-per-row, 2 CSR-stream
-    // pattern SELL with L lanes per row (sellp.hip): values / codes only, columns
-    // from per-slice offset patterns
-    DevBuf<char> sellp_vals;
-    DevBuf<int64_t> sellp_eoff;
-    DevBuf<int32_t> sellp_row0, sellp_pat, sellp_offs;  // pat: {offs start, width} per slice
-    DevBuf<int32_t> sellp_rbase;  // per-row column base (rectangular matrices)
-    DevBuf<double> sellp_vtab;
-    int64_t sellp_slices = 0, sellp_elems = 0, sellp_ntab = 0, sellp_meta_bytes = 0, sellp_stream = 0;
-    bool no_sellp = false;  // e.g. a color-permuted SGS copy (swept in SGS mode)
-    int sellp_L = 0, sellp_vbits = 0;
-    std::vector<int64_t> sellp_seg_slc;
-    // stencil-class storage (scs.hip): one 8/16-bit class id per row, a
-    // dictionary of class stencils over the union of the rows' offsets
-    DevBuf<char> scs_cls;
-    DevBuf<double> scs_dict;
-    DevBuf<int32_t> scs_offs;
-    int64_t scs_k = 0, scs_nclass = 0;
-    int64_t scs_kr = 0;  // offsets before the padding to a multiple of 8 (the x-staged walk stops there)
-    int64_t scs_seg = -1;  // >= 0: only this row segment (a distributed level's halo interior) beside SELL
-    int scs_ib = 0;
-    bool scs_lanes = false;  // one row per wave (few long rows: spmv_scs_lanes_kernel)
-    // x-staged stencil classes on a 3-D grid (scs.hip, spmv_xscs_kernel): per tile
-    // of tx x ty x tz grid points its x window (tile + halo rx/ry/rz) in LDS;
-    // xscs_lo[k] = the window offset of stencil offset k
-    bool xscs = false;
-    int xscs_t[3] = {0, 0, 0}, xscs_r[3] = {0, 0, 0};
-    int xscs_ws = 0;  // LDS row stride of the window (>= wx; padded against bank conflicts)
-    int xscs_tile_src = 0;  // how the tile was chosen: TuneSource (tuning.hpp)
-    bool xscs_fdiv = false;  // the tile's float-reciprocal divisions checked exact (xscs_set_tile)
-    bool xscs_split = false;  // few long rows: eight lanes per row (spmv_xscs_split_kernel)
-    DevBuf<int32_t> xscs_lo;
-    std::vector<int> xscs_steps;  // (dx, dy, dz) of each of the scs_k offsets
-    // grid-transfer classes (gtc.hip) for R/P of a 2x2x2-box hierarchy: an overlay
-    // on the finalized storage used for the modes it supports (gtc_supports)
-    bool gtc_on = false, gtc_r = false;
-    bool gtc_tried = false;  // gtc_attach ran since the last finalize (attach_box_transfers retries nothing)
-    DevBuf<uint8_t> gtc_cls;
-    DevBuf<uint16_t> gtc_dict;  // nclass x ke entries: value index << 8 | step slot
-    DevBuf<double> gtc_vtab;    // the distinct values (<= 256)
-    int gtc_ke = 0, gtc_nce = 0, gtc_ntab = 0, gtc_nclass = 0;
-    // R: per class the first entry of each fine-plane group dz = -1, 0, 1, 2 and the
-    // real entry count (5 bytes; the marching fused restriction of fine.hip)
-    DevBuf<uint8_t> gtc_kdz;
-    // R: per class its value at each of the 32 slots (dz, dy, dx) a 2 x 2 x 2 box
-    // smoothed by the 7-point stencil reaches, +0.0 where the class has no entry
-    // (fine.hip k_fine_rr); empty when some class has an entry outside them
-    DevBuf<double> gtc_wt;
-    int64_t gtc_fg[3] = {0, 0, 0}, gtc_cg[3] = {0, 0, 0};
-    // wide grid-transfer classes (gtx.hip): 16-bit class per row, dictionary of
-    // (window offset, fp64 value) entries in global memory -- every box level
-    bool gtx_on = false, gtx_r = false, gtx_tried = false;
-    DevBuf<uint16_t> gtx_cls;
-    DevBuf<int32_t> gtx_dptr, gtx_dlen, gtx_doff;
-    DevBuf<double> gtx_dval;
-    int64_t gtx_nclass = 0, gtx_nent = 0;
-    int gtx_tile[3] = {0, 0, 0}, gtx_win[3] = {0, 0, 0}, gtx_lo[3] = {0, 0, 0};
-    int64_t gtx_fg[3] = {0, 0, 0}, gtx_cg[3] = {0, 0, 0};
-    bool gtx_fdiv = false;  // the window's float-reciprocal divisions checked exact (at build)
-    // grid hint: the rows are the points of an nx x ny x nz grid, x fastest (0 = none);
-    // set by the stencil generators, the box hierarchy and amg_csr_set_grid
-    // (grid_src 1), else inferred at finalize from the stencil offsets (grid_src 2)
-    int64_t grid[3] = {0, 0, 0};
-    int grid_src = 0;
-    // rank-local matrix of a distributed grid level (dist.hip): its rows are the
-    // owned planes of rframe, its columns the local vector of cframe.  The
-    // x-staged classes and grid-transfer classes then stage ghost planes through
-    // the frame, and their launches split into interior / boundary z-tile ranges
-    // (segments 1 / 0, 2) so the interior runs while the halo is in flight.
-    SlabFrame rframe, cframe;
-    // x-staged SELL (xsell.hip): per group of 4096 rows the x chunks staged in LDS,
-    // per slice fp64 values + 16-bit LDS indices (or 32-bit columns: escape slices)
-    DevBuf<char> xs_data;
-    DevBuf<uint32_t> xs_desc;
-    DevBuf<int32_t> xs_soff, xs_coff, xs_chunks;
-    int64_t xs_groups = 0, xs_bytes = 0, xs_steps = 0, xs_chunk_total = 0, xs_escape_slices = 0;
-    int64_t xs_maxw = 0;  // widest slice (the burst kernel's batch: 7 or 8 steps)
-    // a renumbered copy (reorder.hip): rows in a new order, each row's entries in
-    // the original's stored order with renamed columns -- storages that reorder a
-    // row's entries (DIA, stencil / grid-transfer classes, pattern and aligned SELL)
-    // are not built, so every row sum stays the original's; col_orig = new column ->
-    // original column (the 3x3-block build merges a node's rows by original column)
-    bool order_fixed = false;
-    std::vector<int32_t> col_orig;
-    int kernel = 0;  // SpmvKernel chosen at finalize
-    bool spmv_ready() const { return rp32.get() != nullptr && sched.get() != nullptr; }
-    bool has_sell() const { return sell_desc.get() != nullptr; }
-    bool has_dia() const { return dia_codes.get() != nullptr; }
-    bool has_bsr() const { return bsr_data.get() != nullptr; }
-    bool has_sellp() const { return sellp_vals.get() != nullptr; }
-    bool has_scs() const { return scs_cls.get() != nullptr; }
-    bool has_xs() const { return xs_data.get() != nullptr; }
-    int64_t index_bytes() const { return 12 * nnz + 4 * (nrows + 1); }
-    // matrix bytes one SpMV streams with the chosen kernel (data + metadata)
-    int64_t stream_bytes() const {
-        if (kernel == 3) return dia_cst ? 8 * (int64_t)dia_k : 4 * dia_cw * nrows + 8 * dia_ntab;  // constant: no codes
-        if (kernel == 4) return bsr_steps * (64 * 76) + 8 * (bsr_slices + 1);
-        if (kernel == 5) return sellp_stream;
-        if (kernel == 6) return scs_ib * nrows + 8 * scs_k * scs_nclass + 4 * scs_k;
-        if (kernel == 7) return xs_bytes + 8 * (int64_t)(xs_desc.size() + 1) + 4 * xs_chunk_total + 4 * (xs_groups + 1);
-        if (kernel == 2)
-            return nnz * ((vec_vbits ? vec_vbits / 8 : 8) + (vec_o16 ? 2 : 4)) + 4 * (nrows + 1) + 8 * sell_ntab;
-        return kernel == 1 ? sell_bytes + 12 * (nslices + 1) + 4 * sell_steps + 8 * sell_ntab : index_bytes();
-    }
-};
+// (SlabFrame, the storage structs, GpuCsr and SpmvKernel: gpu_csr.hpp)
 
 // Grid dims (nx, ny, nz) of a square operator of n rows whose stencil has the
 // offsets offs (col - row over some rows); false if no grid explains them.
@@ -273,10 +73,6 @@ extern int g_spmv_format_policy;
 // Value codes for SELL matrices finalized afterwards (1 = when <= 65536
 // distinct values, 0 = always fp64 values)
 extern int g_value_codes;
-enum SpmvKernel : int {
-    SPMV_KERNEL_STREAM = 0, SPMV_KERNEL_SELL = 1, SPMV_KERNEL_VECTOR = 2, SPMV_KERNEL_DIA = 3, SPMV_KERNEL_BSR = 4,
-    SPMV_KERNEL_SELLP = 5, SPMV_KERNEL_SCS = 6, SPMV_KERNEL_XS = 7, SPMV_KERNEL_GTC = 8
-};
 // grid-transfer classes (gtc.hip): fg/cg the fine/coarse grids of a 2x2x2-box
 // level; the row classes of P (fine rows) or R (coarse rows) as (slot, value)
 // lists; gtc_attach builds the overlay storage (true if it applies)
@@ -284,15 +80,11 @@ bool gtc_classes(const GpuCsr &M, bool is_r, const int64_t *fg, const int64_t *c
                  std::vector<std::vector<std::pair<uint8_t, double>>> &dict);
 // which: 1 = R (coarse rows), 0 = P (fine rows), -1 = R if it has fewer rows than columns
 bool gtc_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which = -1);
-void gtc_release(GpuCsr &m);
 // stencil-class storage for structured operators whose rows repeat up to a
 // shift; true if built (scs.hip)
 bool build_scs(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes);
-void scs_release(GpuCsr &m);
 // x-staged SELL for gather-heavy fp64 SELL matrices; true if built (xsell.hip)
 bool build_xs(GpuCsr &m, const std::vector<int64_t> &rp);
-void xs_release(GpuCsr &m);
-void sellp_release(GpuCsr &m);
 // pattern SELL (implicit columns from per-slice offset patterns) for structured
 // operators; true if built (sellp.hip)
 bool build_sellp(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes);
@@ -442,7 +234,6 @@ void fine_resid_restrict(const GpuCsr &A, const GpuCsr &R, const double *f, doub
 bool gtc_supports(const GpuCsr &m, SpmvMode mode);
 // wide grid-transfer classes (gtx.hip); which as gtc_attach
 bool gtx_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which = -1);
-void gtx_release(GpuCsr &m);
 bool gtx_supports(const GpuCsr &m, SpmvMode mode);
 int gtx_mode();
 void spmv_gtx(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
@@ -915,7 +706,7 @@ void perm_gather_df(double *f0, double *t, const double *in, const int32_t *p, c
 
 // the zero-guess fold decision of one level (RESID0 + ADD0 instead of v = d*f)
 // m's DIA codes are a constant 7- or 27-point stencil on an nx x ny x nz grid (nx
-// even), truncated at the faces: fills m.dia_cst* (sgs27.hip)
+// even), truncated at the faces: fills m.dia.cst* (sgs27.hip)
 bool dia_constant(GpuCsr &m);
 bool fold_level(const CsrOp *A, const DiagOp *D, const CsrOp *P, bool fold_zero_guess, bool v_zero, int64_t steps);
 // the level takes its first Jacobi step from zero unfolded (smooth(): t = d*f), so
@@ -928,7 +719,7 @@ inline bool level_wants_df(const CsrOp *A, const DiagOp *D, const CsrOp *P, bool
 bool setdf_enabled();
 // R serves SPMV_SETDF (a grid-transfer overlay of either width, pattern SELL or 3x3 blocks)
 inline bool r_has_setdf(const CsrOp *R) {
-    return R && ((R->m.gtx_on && R->m.gtx_r) || (R->m.gtc_on && R->m.gtc_r) || R->m.kernel == SPMV_KERNEL_SELLP ||
+    return R && ((R->m.gtx.built() && R->m.gtx.r) || (R->m.gtc.built() && R->m.gtc.r) || R->m.kernel == SPMV_KERNEL_SELLP ||
                  R->m.kernel == SPMV_KERNEL_BSR);
 }
 

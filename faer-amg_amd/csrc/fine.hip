@@ -544,7 +544,7 @@ __global__ __launch_bounds__(256) void k_fine_resid_restrict(FineRrArgs a) {
 //   R's terms without value-table lookups or masks: every class's entries lie in
 //     the 32 slots (dz, dy, dx) a 2 x 2 x 2 box smoothed by the 7-point stencil
 //     reaches (4 at dz = -1, 12 at dz = 0, 12 at dz = 1, 4 at dz = 2), so each
-//     class is 32 fp64 weights in LDS (gtc_wt, +0.0 where the class has no
+//     class is 32 fp64 weights in LDS (gtc.wt, +0.0 where the class has no
 //     entry) and a plane adds 4 or 12 fma terms per chain: an absent slot adds
 //     fma(+0.0, r, acc) = acc (r finite, the accumulator never -0.0), so every
 //     chain is the class's entries in ascending (dz, dy, dx) order, bitwise
@@ -1022,17 +1022,17 @@ static int fine_rr_occupancy(size_t dyn) {
 
 bool fine_resid_restrict_ok(const GpuCsr &A, const GpuCsr &R, const SpmvEpi &epi, const SpmvEpi &epic) {
     if (flag(FLAG_FINE_FUSE) == 0 || !dia7_cst_dk(A, epi)) return false;
-    if (!R.gtc_on || !R.gtc_r || R.rframe.on() || R.cframe.on() || R.gtc_nce > FR_DMAX || R.gtc_ntab > 256 ||
-        !R.gtc_kdz.get() || R.gtc_ke % 8 != 0)
+    if (!R.gtc.built() || !R.gtc.r || R.rframe.on() || R.cframe.on() || R.gtc.nce > FR_DMAX || R.gtc.ntab > 256 ||
+        !R.gtc.kdz.get() || R.gtc.ke % 8 != 0)
         return false;
     // the coarse level's d coded (8-bit) or one value: no global load in the plane loop
     if (!epic.y2 || !epic.dc) return false;
     for (int q = 0; q < 3; q++)
-        if (R.gtc_fg[q] != A.dia_cst_n[q] || R.gtc_cg[q] != (R.gtc_fg[q] + 1) / 2) return false;
+        if (R.gtc.fg[q] != A.dia.cst_n[q] || R.gtc.cg[q] != (R.gtc.fg[q] + 1) / 2) return false;
     // even nx: the 16-B units of a window row never straddle the end of a grid row
     // except where the kernels shift them (an odd nx runs the unfused launches)
-    if (R.gtc_fg[0] % 2 != 0) return false;
-    return A.nrows == R.ncols && R.nrows == R.gtc_cg[0] * R.gtc_cg[1] * R.gtc_cg[2];
+    if (R.gtc.fg[0] % 2 != 0) return false;
+    return A.nrows == R.ncols && R.nrows == R.gtc.cg[0] * R.gtc.cg[1] * R.gtc.cg[2];
 }
 
 // workgroups of k_fine_rr per CU (cached)
@@ -1060,11 +1060,11 @@ static bool fine_rr_v1() {
 static void fine_rr2(const GpuCsr &A, const GpuCsr &R, const double *f, double dk, double *fc, const SpmvEpi &epic,
                      hipStream_t s) {
     FineRr2Args a{};
-    a.cls = R.gtc_cls.get();
-    a.wt = R.gtc_wt.get();
-    a.nclass = R.gtc_nclass;
-    a.nx = (int)R.gtc_fg[0]; a.ny = (int)R.gtc_fg[1]; a.nz = (int)R.gtc_fg[2];
-    a.cx = (int)R.gtc_cg[0]; a.cy = (int)R.gtc_cg[1]; a.cz = (int)R.gtc_cg[2];
+    a.cls = R.gtc.cls.get();
+    a.wt = R.gtc.wt.get();
+    a.nclass = R.gtc.nclass;
+    a.nx = (int)R.gtc.fg[0]; a.ny = (int)R.gtc.fg[1]; a.nz = (int)R.gtc.fg[2];
+    a.cx = (int)R.gtc.cg[0]; a.cy = (int)R.gtc.cg[1]; a.cz = (int)R.gtc.cg[2];
     a.ntx = (int)ceil_div(a.cx, R2_TX);
     a.nty = (int)ceil_div(a.cy, R2_TY);
     a.f = f;
@@ -1079,7 +1079,7 @@ static void fine_rr2(const GpuCsr &A, const GpuCsr &R, const double *f, double d
         a.dtc = epic.dt;
     }
     a.dk = dk;
-    for (int k = 0; k < 7; k++) a.cst[k] = A.dia_cst_v[k];
+    for (int k = 0; k < 7; k++) a.cst[k] = A.dia.cst_v[k];
     FINE_DBG_READ(a);
     const int64_t ntxy = (int64_t)a.ntx * a.nty;
     // occupancy at a typical run length, then the run length for one round of workgroups
@@ -1094,7 +1094,7 @@ static void fine_rr2(const GpuCsr &A, const GpuCsr &R, const double *f, double d
 
 void fine_resid_restrict(const GpuCsr &A, const GpuCsr &R, const double *f, double dk, double *fc,
                          const SpmvEpi &epic, hipStream_t s) {
-    if (!fine_rr_v1() && R.gtc_wt.get() && R.gtc_nclass <= R2_CMAX && R.gtc_fg[0] * R.gtc_fg[1] < (int64_t(1) << 31)) {
+    if (!fine_rr_v1() && R.gtc.wt.get() && R.gtc.nclass <= R2_CMAX && R.gtc.fg[0] * R.gtc.fg[1] < (int64_t(1) << 31)) {
         fine_rr2(A, R, f, dk, fc, epic, s);
         const int64_t n = A.nrows, nc = R.nrows;
         log_launch("fine-rr", SPMV_KERNEL_DIA, -1, n, 8 * n + 16 * nc + nc + (epic.dc && !(epic.dk != 0.0 && flag(FLAG_DIA_DK) != 0) ? nc : 0),
@@ -1102,16 +1102,16 @@ void fine_resid_restrict(const GpuCsr &A, const GpuCsr &R, const double *f, doub
         return;
     }
     FineRrArgs a{};
-    a.cls = R.gtc_cls.get();
-    a.dict = R.gtc_dict.get();
-    a.vtab = R.gtc_vtab.get();
-    a.kdz = R.gtc_kdz.get();
-    a.ke = R.gtc_ke;
-    a.nce = R.gtc_nce;
-    a.ntab = R.gtc_ntab;
-    a.nclass = R.gtc_nclass;
-    a.nx = (int)R.gtc_fg[0]; a.ny = (int)R.gtc_fg[1]; a.nz = (int)R.gtc_fg[2];
-    a.cx = (int)R.gtc_cg[0]; a.cy = (int)R.gtc_cg[1]; a.cz = (int)R.gtc_cg[2];
+    a.cls = R.gtc.cls.get();
+    a.dict = R.gtc.dict.get();
+    a.vtab = R.gtc.vtab.get();
+    a.kdz = R.gtc.kdz.get();
+    a.ke = R.gtc.ke;
+    a.nce = R.gtc.nce;
+    a.ntab = R.gtc.ntab;
+    a.nclass = R.gtc.nclass;
+    a.nx = (int)R.gtc.fg[0]; a.ny = (int)R.gtc.fg[1]; a.nz = (int)R.gtc.fg[2];
+    a.cx = (int)R.gtc.cg[0]; a.cy = (int)R.gtc.cg[1]; a.cz = (int)R.gtc.cg[2];
     a.ntx = (int)ceil_div(a.cx, FR_TX);
     a.nty = (int)ceil_div(a.cy, FR_TY);
     a.f = f;
@@ -1127,7 +1127,7 @@ void fine_resid_restrict(const GpuCsr &A, const GpuCsr &R, const double *f, doub
         a.dtc = epic.dt;
     }
     a.dk = dk;
-    for (int k = 0; k < 7; k++) a.cst[k] = A.dia_cst_v[k];
+    for (int k = 0; k < 7; k++) a.cst[k] = A.dia.cst_v[k];
     FINE_DBG_READ(a);
     const int64_t ntxy = (int64_t)a.ntx * a.nty;
     // occupancy with the dictionary part of the dynamic LDS (the per-plane class
@@ -1150,14 +1150,14 @@ void fine_resid_restrict(const GpuCsr &A, const GpuCsr &R, const double *f, doub
 
 bool fine_interp_jacobi_ok(const GpuCsr &A, const GpuCsr &P, const SpmvEpi &epi) {
     if (flag(FLAG_FINE_FUSE) == 0 || !dia7_cst_dk(A, epi)) return false;
-    if (!P.gtc_on || P.gtc_r || P.rframe.on() || P.cframe.on() || P.gtc_nce > 512 ||
-        (P.gtc_ke != 4 && P.gtc_ke != 8) ||
-        P.gtc_ntab > 256)
+    if (!P.gtc.built() || P.gtc.r || P.rframe.on() || P.cframe.on() || P.gtc.nce > 512 ||
+        (P.gtc.ke != 4 && P.gtc.ke != 8) ||
+        P.gtc.ntab > 256)
         return false;
     for (int q = 0; q < 3; q++)
-        if (P.gtc_fg[q] != A.dia_cst_n[q] || P.gtc_cg[q] != (P.gtc_fg[q] + 1) / 2) return false;
-    if (P.gtc_fg[0] % 2 != 0) return false;  // even nx (16-B units of two points in one box)
-    return A.nrows == P.nrows && P.ncols == P.gtc_cg[0] * P.gtc_cg[1] * P.gtc_cg[2];
+        if (P.gtc.fg[q] != A.dia.cst_n[q] || P.gtc.cg[q] != (P.gtc.fg[q] + 1) / 2) return false;
+    if (P.gtc.fg[0] % 2 != 0) return false;  // even nx (16-B units of two points in one box)
+    return A.nrows == P.nrows && P.ncols == P.gtc.cg[0] * P.gtc.cg[1] * P.gtc.cg[2];
 }
 
 // workgroups of k_fine_pj per CU (cached)
@@ -1183,19 +1183,19 @@ static bool fine_pj_v1() {
 static void fine_pj2(const GpuCsr &A, const GpuCsr &P, const double *vc, const double *f, double dk, double *out,
                      hipStream_t s) {
     FinePj2Args a{};
-    a.cls = P.gtc_cls.get();
-    a.dict = P.gtc_dict.get();
-    a.vtab = P.gtc_vtab.get();
-    a.nclass = P.gtc_nclass;
-    a.nx = (int)P.gtc_fg[0]; a.ny = (int)P.gtc_fg[1]; a.nz = (int)P.gtc_fg[2];
-    a.cx = (int)P.gtc_cg[0]; a.cy = (int)P.gtc_cg[1]; a.cz = (int)P.gtc_cg[2];
+    a.cls = P.gtc.cls.get();
+    a.dict = P.gtc.dict.get();
+    a.vtab = P.gtc.vtab.get();
+    a.nclass = P.gtc.nclass;
+    a.nx = (int)P.gtc.fg[0]; a.ny = (int)P.gtc.fg[1]; a.nz = (int)P.gtc.fg[2];
+    a.cx = (int)P.gtc.cg[0]; a.cy = (int)P.gtc.cg[1]; a.cz = (int)P.gtc.cg[2];
     a.ntx = (int)ceil_div(a.nx, J2_TX);
     a.nty = (int)ceil_div(a.ny, J2_TY);
     a.vc = vc;
     a.f = f;
     a.out = out;
     a.dk = dk;
-    for (int k = 0; k < 7; k++) a.cst[k] = A.dia_cst_v[k];
+    for (int k = 0; k < 7; k++) a.cst[k] = A.dia.cst_v[k];
     FINE_DBG_READ(a);
     const int64_t ntxy = (int64_t)a.ntx * a.nty;
     const int64_t want = (int64_t)fine_pj2_occupancy() * std::max(A.ctx ? A.ctx->num_cus : 256, 1);
@@ -1209,7 +1209,7 @@ static void fine_pj2(const GpuCsr &A, const GpuCsr &P, const double *vc, const d
 
 void fine_interp_jacobi(const GpuCsr &A, const GpuCsr &P, const double *vc, const double *f, double dk, double *out,
                         hipStream_t s) {
-    if (!fine_pj_v1() && P.gtc_ke == 4 && P.gtc_nclass <= J2_CMAX && P.gtc_fg[0] * P.gtc_fg[1] < (int64_t(1) << 31)) {
+    if (!fine_pj_v1() && P.gtc.ke == 4 && P.gtc.nclass <= J2_CMAX && P.gtc.fg[0] * P.gtc.fg[1] < (int64_t(1) << 31)) {
         fine_pj2(A, P, vc, f, dk, out, s);
         const int64_t n = A.nrows;
         log_launch("fine-pj", SPMV_KERNEL_DIA, -1, n, 8 * n + 8 * P.ncols + 8 * n + n,
@@ -1217,21 +1217,21 @@ void fine_interp_jacobi(const GpuCsr &A, const GpuCsr &P, const double *vc, cons
         return;
     }
     FinePjArgs a{};
-    a.cls = P.gtc_cls.get();
-    a.dict = P.gtc_dict.get();
-    a.vtab = P.gtc_vtab.get();
-    a.ke = P.gtc_ke;
-    a.nce = P.gtc_nce;
-    a.ntab = P.gtc_ntab;
-    a.nx = (int)P.gtc_fg[0]; a.ny = (int)P.gtc_fg[1]; a.nz = (int)P.gtc_fg[2];
-    a.cx = (int)P.gtc_cg[0]; a.cy = (int)P.gtc_cg[1]; a.cz = (int)P.gtc_cg[2];
+    a.cls = P.gtc.cls.get();
+    a.dict = P.gtc.dict.get();
+    a.vtab = P.gtc.vtab.get();
+    a.ke = P.gtc.ke;
+    a.nce = P.gtc.nce;
+    a.ntab = P.gtc.ntab;
+    a.nx = (int)P.gtc.fg[0]; a.ny = (int)P.gtc.fg[1]; a.nz = (int)P.gtc.fg[2];
+    a.cx = (int)P.gtc.cg[0]; a.cy = (int)P.gtc.cg[1]; a.cz = (int)P.gtc.cg[2];
     a.ntx = (int)ceil_div(a.nx, FP_TX);
     a.nty = (int)ceil_div(a.ny, FP_TY);
     a.vc = vc;
     a.f = f;
     a.out = out;
     a.dk = dk;
-    for (int k = 0; k < 7; k++) a.cst[k] = A.dia_cst_v[k];
+    for (int k = 0; k < 7; k++) a.cst[k] = A.dia.cst_v[k];
     // one round of workgroups over the chip; an even run of planes per workgroup
     const int64_t ntxy = (int64_t)a.ntx * a.nty;
     const int64_t want = (int64_t)fine_pj_occupancy() * std::max(A.ctx ? A.ctx->num_cus : 256, 1);

@@ -457,16 +457,6 @@ __global__ __launch_bounds__(256) void k_gtc_restrict_march(GtcArgs a) {
 
 // ------------------------------------------------------------ build / dispatch
 
-void gtc_release(GpuCsr &m) {
-    m.gtc_cls.release();
-    m.gtc_dict.release();
-    m.gtc_vtab.release();
-    m.gtc_kdz.release();
-    m.gtc_wt.release();
-    m.gtc_ke = m.gtc_nce = m.gtc_ntab = m.gtc_nclass = 0;
-    m.gtc_r = m.gtc_on = false;
-}
-
 // FAMG_GTC=0: keep the finalize-time storage for R and P
 static bool gtc_enabled() {
     static const bool on = env_not_zero("FAMG_GTC");
@@ -474,8 +464,8 @@ static bool gtc_enabled() {
 }
 
 bool gtc_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which) {
-    gtc_release(m);
-    m.gtc_tried = true;
+    m.gtc = {};
+    m.tried_gtc = true;
     if (!gtc_enabled() || m.nnz >= (int64_t(1) << 31)) return false;
     const bool is_r = which < 0 ? m.nrows < m.ncols : which == 1;
     // a rank-local P starts at an even fine plane (its tiles' four fine planes
@@ -516,12 +506,12 @@ bool gtc_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which) {
     std::vector<double> vt(vals.size());
     for (size_t q = 0; q < vals.size(); q++) std::memcpy(&vt[q], &vals[q], 8);
     hipStream_t s = m.ctx->stream;
-    m.gtc_cls.resize(cls.size());
-    m.gtc_dict.resize(hd.size());
-    m.gtc_vtab.resize(vt.size());
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc_cls.get(), cls.data(), cls.size(), hipMemcpyHostToDevice, s));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc_dict.get(), hd.data(), hd.size() * 2, hipMemcpyHostToDevice, s));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc_vtab.get(), vt.data(), vt.size() * 8, hipMemcpyHostToDevice, s));
+    m.gtc.cls.resize(cls.size());
+    m.gtc.dict.resize(hd.size());
+    m.gtc.vtab.resize(vt.size());
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc.cls.get(), cls.data(), cls.size(), hipMemcpyHostToDevice, s));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc.dict.get(), hd.data(), hd.size() * 2, hipMemcpyHostToDevice, s));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc.vtab.get(), vt.data(), vt.size() * 8, hipMemcpyHostToDevice, s));
     if (is_r && ke <= 255) {  // per class: where each fine plane's entries start (slots ascend in dz)
         std::vector<uint8_t> kdz(dict.size() * 5);
         for (size_t c = 0; c < dict.size(); c++) {
@@ -532,8 +522,8 @@ bool gtc_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which) {
             }
             kdz[c * 5 + 4] = (uint8_t)dict[c].size();
         }
-        m.gtc_kdz.resize(kdz.size());
-        FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc_kdz.get(), kdz.data(), kdz.size(), hipMemcpyHostToDevice, s));
+        m.gtc.kdz.resize(kdz.size());
+        FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc.kdz.get(), kdz.data(), kdz.size(), hipMemcpyHostToDevice, s));
         // the 32-slot weights (fine.hip k_fine_rr): every entry in the slots a
         // 2 x 2 x 2 box smoothed by the 7-point stencil reaches, else none
         static const int8_t pat[64] = {
@@ -556,21 +546,21 @@ bool gtc_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which) {
                 wt[c * 32 + pat[e.first]] = e.second;
             }
         if (fits) {
-            m.gtc_wt.resize(wt.size());
-            FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc_wt.get(), wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
+            m.gtc.wt.resize(wt.size());
+            FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc.wt.get(), wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
         }
     }
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
-    m.gtc_nclass = (int)dict.size();
-    m.gtc_ke = (int)ke;
-    m.gtc_nce = (int)(dict.size() * ke);
-    m.gtc_ntab = (int)vt.size();
-    m.gtc_r = is_r;
+    m.gtc.nclass = (int)dict.size();
+    m.gtc.ke = (int)ke;
+    m.gtc.nce = (int)(dict.size() * ke);
+    m.gtc.ntab = (int)vt.size();
+    m.gtc.r = is_r;
     for (int q = 0; q < 3; q++) {
-        m.gtc_fg[q] = fg[q];
-        m.gtc_cg[q] = cg[q];
+        m.gtc.fg[q] = fg[q];
+        m.gtc.cg[q] = cg[q];
     }
-    m.gtc_on = true;
+    m.gtc.on = true;
     return true;
 }
 
@@ -580,10 +570,10 @@ void attach_box_transfers(const GpuCsr &Af, const GpuCsr &Ac, GpuCsr &R, GpuCsr 
         if (fg[q] <= 0 || cg[q] != (fg[q] + 1) / 2) return;
     if (fg[0] * fg[1] * fg[2] != Af.nrows || cg[0] * cg[1] * cg[2] != Ac.nrows) return;
     if (P.nrows != Af.nrows || P.ncols != Ac.nrows || R.nrows != Ac.nrows || R.ncols != Af.nrows) return;
-    if (!P.gtc_on && !P.gtc_tried) gtc_attach(P, fg, cg, 0);
-    if (!R.gtc_on && !R.gtc_tried) gtc_attach(R, fg, cg, 1);
-    if ((!P.gtc_on || gtx_mode() == 2) && !P.gtx_on && !P.gtx_tried) gtx_attach(P, fg, cg, 0);
-    if ((!R.gtc_on || gtx_mode() == 2) && !R.gtx_on && !R.gtx_tried) gtx_attach(R, fg, cg, 1);
+    if (!P.gtc.built() && !P.tried_gtc) gtc_attach(P, fg, cg, 0);
+    if (!R.gtc.built() && !R.tried_gtc) gtc_attach(R, fg, cg, 1);
+    if ((!P.gtc.built() || gtx_mode() == 2) && !P.gtx.built() && !P.tried_gtx) gtx_attach(P, fg, cg, 0);
+    if ((!R.gtc.built() || gtx_mode() == 2) && !R.gtx.built() && !R.tried_gtx) gtx_attach(R, fg, cg, 1);
 }
 
 // fine points per lane along z in the P kernel (FAMG_GTC_TZ=8: eight)
@@ -752,7 +742,7 @@ static bool gtc_march_r() {
 }
 
 bool gtc_supports(const GpuCsr &m, SpmvMode mode) {
-    return m.gtc_r ? (mode == SPMV_SET || mode == SPMV_SETDF) : (mode == SPMV_SET || mode == SPMV_ADD || mode == SPMV_ADD0);
+    return m.gtc.r ? (mode == SPMV_SET || mode == SPMV_SETDF) : (mode == SPMV_SET || mode == SPMV_ADD || mode == SPMV_ADD0);
 }
 
 // The z-tiles [ta, tb) of a launch whose column windows [w0(t), w0(t) + wz) read
@@ -769,13 +759,13 @@ static void interior_tiles(int ntz, int wz, int kz_own, int kz_lo, int kz_hi, F 
 void spmv_gtc(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
               int64_t seg) {
     GtcArgs a{};
-    a.cls = m.gtc_cls.get();
-    a.dict = m.gtc_dict.get();
-    a.vtab = m.gtc_vtab.get();
-    a.ke = m.gtc_ke;
-    a.nce = m.gtc_nce;
-    a.ntab = m.gtc_ntab;
-    const int64_t *rg = m.gtc_r ? m.gtc_cg : m.gtc_fg, *kg = m.gtc_r ? m.gtc_fg : m.gtc_cg;
+    a.cls = m.gtc.cls.get();
+    a.dict = m.gtc.dict.get();
+    a.vtab = m.gtc.vtab.get();
+    a.ke = m.gtc.ke;
+    a.nce = m.gtc.nce;
+    a.ntab = m.gtc.ntab;
+    const int64_t *rg = m.gtc.r ? m.gtc.cg : m.gtc.fg, *kg = m.gtc.r ? m.gtc.fg : m.gtc.cg;
     a.rx = (int)rg[0]; a.ry = (int)rg[1]; a.rz = (int)rg[2];
     a.kx = (int)kg[0]; a.ky = (int)kg[1]; a.kz = (int)kg[2];
     a.kz_lo = 0; a.kz_hi = a.kz; a.rz0 = 0; a.kz0 = 0; a.add_lo = a.add_hi = 0;
@@ -804,7 +794,7 @@ void spmv_gtc(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
         z0 = seg < 0 || seg == 0 ? 0 : seg == 1 ? ta : tb;
         z1 = seg < 0 || seg == 2 ? ntz : seg == 1 ? tb : ta;
     };
-    if (m.gtc_r) {
+    if (m.gtc.r) {
         FAMG_REQUIRE(mode == SPMV_SET || mode == SPMV_SETDF, AMG_ERR_UNSUPPORTED, "grid-transfer R: SET / SETDF only");
         FAMG_REQUIRE(mode != SPMV_SETDF || (epi.y2 && (epi.d || epi.dc || epi.dk != 0.0)), AMG_ERR_INVALID,
                      "SETDF needs y2 and d");
@@ -890,16 +880,16 @@ void spmv_gtc(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
 // grid-transfer classes of a single-GPU level (no slab frame)
 void spmm_gtc(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
               hipStream_t s) {
-    FAMG_REQUIRE(m.gtc_on && !m.rframe.on() && gtc_supports(m, mode) && mode != SPMV_ADD0 && mode != SPMV_SETDF,
+    FAMG_REQUIRE(m.gtc.built() && !m.rframe.on() && gtc_supports(m, mode) && mode != SPMV_ADD0 && mode != SPMV_SETDF,
                  AMG_ERR_UNSUPPORTED, "grid-transfer SpMM: SET (R, P) or ADD (P) on a single-GPU level");
     GtcArgs a{};
-    a.cls = m.gtc_cls.get();
-    a.dict = m.gtc_dict.get();
-    a.vtab = m.gtc_vtab.get();
-    a.ke = m.gtc_ke;
-    a.nce = m.gtc_nce;
-    a.ntab = m.gtc_ntab;
-    const int64_t *rg = m.gtc_r ? m.gtc_cg : m.gtc_fg, *kg = m.gtc_r ? m.gtc_fg : m.gtc_cg;
+    a.cls = m.gtc.cls.get();
+    a.dict = m.gtc.dict.get();
+    a.vtab = m.gtc.vtab.get();
+    a.ke = m.gtc.ke;
+    a.nce = m.gtc.nce;
+    a.ntab = m.gtc.ntab;
+    const int64_t *rg = m.gtc.r ? m.gtc.cg : m.gtc.fg, *kg = m.gtc.r ? m.gtc.fg : m.gtc.cg;
     a.rx = (int)rg[0]; a.ry = (int)rg[1]; a.rz = (int)rg[2];
     a.kx = (int)kg[0]; a.ky = (int)kg[1]; a.kz = (int)kg[2];
     a.kz_lo = 0; a.kz_hi = a.kz; a.rz0 = 0; a.kz0 = 0; a.add_lo = a.add_hi = 0;
@@ -909,7 +899,7 @@ void spmm_gtc(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t 
         const int kb = (int)std::min<int64_t>(8, k - c0);
         a.x = x + c0 * ldx;
         a.y = y + c0 * ldy;
-        if (m.gtc_r) {
+        if (m.gtc.r) {
             a.ntx = (int)ceil_div(a.rx, GR_TX);
             a.nty = (int)ceil_div(a.ry, GR_TY);
             const int rtz = gtc_rtz() == 4 ? 4 : 2;

@@ -308,16 +308,6 @@ __global__ __launch_bounds__(256) void k_gtx_restrict(GtxArgs a) {
 
 // ------------------------------------------------------------ build / dispatch
 
-void gtx_release(GpuCsr &m) {
-    m.gtx_cls.release();
-    m.gtx_dptr.release();
-    m.gtx_dlen.release();
-    m.gtx_doff.release();
-    m.gtx_dval.release();
-    m.gtx_on = m.gtx_r = false;
-    m.gtx_nclass = m.gtx_nent = 0;
-}
-
 // FAMG_GTX: 0 off; 1 (default) levels whose R/P the 8-bit grid-transfer classes
 // (gtc.hip) cannot take; 2 every box level (A/B against gtc on level 0)
 int gtx_mode() {
@@ -342,7 +332,7 @@ static bool gtx_beats_storage(GpuCsr &m) {
     if (how != 1) return rows >= (int64_t(1) << 18);
     // R of the small levels (<= 65536 coarse rows of hundreds of entries) loses in the cycle
     // even where an isolated timing has it ahead (R_2 of the 256^3 cycle: 32.5 vs 21.9 + 4.6 us)
-    if (m.gtx_r && m.nrows <= 65536) return false;
+    if (m.gtx.r && m.nrows <= 65536) return false;
     hipStream_t s = m.ctx->stream;
     DevBuf<double> x(m.ncols), y(m.nrows), y2(m.nrows);
     FAMG_CHECK_HIP(hipMemsetAsync(x.get(), 0, m.ncols * sizeof(double), s));
@@ -352,10 +342,10 @@ static bool gtx_beats_storage(GpuCsr &m) {
     FAMG_CHECK_HIP(hipEventCreate(&e1));
     float ms[2] = {0.f, 0.f};
     for (int k = 0; k < 2; k++) {
-        m.gtx_on = k == 1;
+        m.gtx.on = k == 1;
         auto run = [&] {
             spmv(m, x.get(), y.get(), SPMV_SET, SpmvEpi{}, s);
-            if (m.gtx_r && k == 0) vec_mul(y2.get(), y.get(), y.get(), m.nrows, s);  // the d*f pass SETDF saves
+            if (m.gtx.r && k == 0) vec_mul(y2.get(), y.get(), y.get(), m.nrows, s);  // the d*f pass SETDF saves
         };
         run();
         FAMG_CHECK_HIP(hipEventRecord(e0, s));
@@ -366,13 +356,13 @@ static bool gtx_beats_storage(GpuCsr &m) {
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    m.gtx_on = true;
+    m.gtx.on = true;
     return ms[1] < 0.9f * ms[0];  // a clear win only (launch-bound small levels time noisily)
 }
 
 bool gtx_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which) {
-    gtx_release(m);
-    m.gtx_tried = true;
+    m.gtx = {};
+    m.tried_gtx = true;
     if (gtx_mode() == 0 || m.nnz >= (int64_t(1) << 31) || m.nrows <= 0 || m.nnz <= 0) return false;
     const bool is_r = which < 0 ? m.nrows < m.ncols : which == 1;
     const int64_t rx = is_r ? cg[0] : fg[0], ry = is_r ? cg[1] : fg[1], rz = is_r ? cg[2] : fg[2];  // row grid
@@ -543,47 +533,47 @@ bool gtx_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which) {
         dlen[c] = (int32_t)(doff.size() - dptr[c]);
         if (doff.size() >= (size_t)INT32_MAX / 2) return false;
     }
-    m.gtx_cls.resize(n);
-    m.gtx_dptr.resize(C);
-    m.gtx_dlen.resize(C);
-    m.gtx_doff.resize(doff.size() + 4);
-    m.gtx_dval.resize(dval.size() + 4);
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtx_cls.get(), cls.data(), n * 2, hipMemcpyHostToDevice, s));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtx_dptr.get(), dptr.data(), C * 4, hipMemcpyHostToDevice, s));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtx_dlen.get(), dlen.data(), C * 4, hipMemcpyHostToDevice, s));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtx_doff.get(), doff.data(), doff.size() * 4, hipMemcpyHostToDevice, s));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtx_dval.get(), dval.data(), dval.size() * 8, hipMemcpyHostToDevice, s));
+    m.gtx.cls.resize(n);
+    m.gtx.dptr.resize(C);
+    m.gtx.dlen.resize(C);
+    m.gtx.doff.resize(doff.size() + 4);
+    m.gtx.dval.resize(dval.size() + 4);
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtx.cls.get(), cls.data(), n * 2, hipMemcpyHostToDevice, s));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtx.dptr.get(), dptr.data(), C * 4, hipMemcpyHostToDevice, s));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtx.dlen.get(), dlen.data(), C * 4, hipMemcpyHostToDevice, s));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtx.doff.get(), doff.data(), doff.size() * 4, hipMemcpyHostToDevice, s));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.gtx.dval.get(), dval.data(), dval.size() * 8, hipMemcpyHostToDevice, s));
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
-    m.gtx_nclass = C;
-    m.gtx_nent = (int64_t)doff.size();
+    m.gtx.nclass = C;
+    m.gtx.nent = (int64_t)doff.size();
     for (int q = 0; q < 3; q++) {
-        m.gtx_tile[q] = tile[q];
-        m.gtx_win[q] = wdim[q];
-        m.gtx_lo[q] = lo[q];
-        m.gtx_fg[q] = fg[q];
-        m.gtx_cg[q] = cg[q];
+        m.gtx.tile[q] = tile[q];
+        m.gtx.win[q] = wdim[q];
+        m.gtx.lo[q] = lo[q];
+        m.gtx.fg[q] = fg[q];
+        m.gtx.cg[q] = cg[q];
     }
-    m.gtx_r = is_r;
+    m.gtx.r = is_r;
     {  // the staging loops' float-reciprocal divisions, checked once at build
         const int wx = wdim[0], wy = wdim[1], wz = wdim[2], tx = std::max(tile[0], 1), ty = std::max(tile[1], 1);
-        m.gtx_fdiv = fdiv_exact(wx * wy * wz + 256 * 8, wx, 1.0f / (float)wx) &&
+        m.gtx.fdiv = fdiv_exact(wx * wy * wz + 256 * 8, wx, 1.0f / (float)wx) &&
                      fdiv_exact((wx * wy * wz + 256 * 8) / wx + 1, wy, 1.0f / (float)wy) &&
                      fdiv_exact(1024, tx, 1.0f / (float)tx) && fdiv_exact(1024 / tx + 1, ty, 1.0f / (float)ty);
     }
-    m.gtx_on = true;
+    m.gtx.on = true;
     // keep the classes only where they beat the storage underneath (timed on
     // scratch vectors; R is charged with the d*f pass its SETDF epilogue saves):
     // the small Galerkin levels' long rows (R_3: ~490 entries, P_4 from a 16^3
     // grid: 8 tiles) run a lane per row and lose to the lanes-per-row kernels
     if (!gtx_beats_storage(m)) {
-        gtx_release(m);
+        m.gtx = {};
         return false;
     }
     return true;
 }
 
 bool gtx_supports(const GpuCsr &m, SpmvMode mode) {
-    return m.gtx_r ? (mode == SPMV_SET || mode == SPMV_SETDF)
+    return m.gtx.r ? (mode == SPMV_SET || mode == SPMV_SETDF)
                    : (mode == SPMV_SET || mode == SPMV_ADD || mode == SPMV_ADD0);
 }
 
@@ -606,20 +596,20 @@ void spmv_gtx(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
               int64_t seg) {
     FAMG_REQUIRE(gtx_supports(m, mode), AMG_ERR_UNSUPPORTED, "wide grid-transfer classes: unsupported epilogue");
     GtxArgs a{};
-    a.cls = m.gtx_cls.get();
-    a.dptr = m.gtx_dptr.get();
-    a.dlen = m.gtx_dlen.get();
-    a.doff = m.gtx_doff.get();
-    a.dval = m.gtx_dval.get();
-    const int64_t *rg = m.gtx_r ? m.gtx_cg : m.gtx_fg, *kg = m.gtx_r ? m.gtx_fg : m.gtx_cg;
+    a.cls = m.gtx.cls.get();
+    a.dptr = m.gtx.dptr.get();
+    a.dlen = m.gtx.dlen.get();
+    a.doff = m.gtx.doff.get();
+    a.dval = m.gtx.dval.get();
+    const int64_t *rg = m.gtx.r ? m.gtx.cg : m.gtx.fg, *kg = m.gtx.r ? m.gtx.fg : m.gtx.cg;
     a.rx = (int)rg[0]; a.ry = (int)rg[1]; a.rz = (int)rg[2];
     a.kx = (int)kg[0]; a.ky = (int)kg[1]; a.kz = (int)kg[2];
-    a.tx = m.gtx_tile[0]; a.ty = m.gtx_tile[1]; a.tz = m.gtx_tile[2];
-    a.wx = m.gtx_win[0]; a.wy = m.gtx_win[1]; a.wz = m.gtx_win[2];
-    a.lox = m.gtx_lo[0]; a.loy = m.gtx_lo[1]; a.loz = m.gtx_lo[2];
+    a.tx = m.gtx.tile[0]; a.ty = m.gtx.tile[1]; a.tz = m.gtx.tile[2];
+    a.wx = m.gtx.win[0]; a.wy = m.gtx.win[1]; a.wz = m.gtx.win[2];
+    a.lox = m.gtx.lo[0]; a.loy = m.gtx.lo[1]; a.loz = m.gtx.lo[2];
     a.rwx = 1.0f / (float)a.wx; a.rwy = 1.0f / (float)a.wy;
     a.rtx = 1.0f / (float)std::max(a.tx, 1); a.rty = 1.0f / (float)std::max(a.ty, 1);
-    FAMG_REQUIRE(m.gtx_fdiv, AMG_ERR_UNSUPPORTED, "wide grid-transfer classes: window too large for the float divisions");
+    FAMG_REQUIRE(m.gtx.fdiv, AMG_ERR_UNSUPPORTED, "wide grid-transfer classes: window too large for the float divisions");
     a.kz_lo = 0; a.kz_hi = a.kz; a.rz0 = 0; a.kz0 = 0; a.add_lo = a.add_hi = 0;
     if (m.rframe.on()) {
         a.rz = (int)m.rframe.nz;
@@ -645,7 +635,7 @@ void spmv_gtx(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
     const int ntz = (int)ceil_div(a.rz, a.tz);
     const size_t lds = (size_t)a.wx * a.wy * a.wz * sizeof(double);
     int z0 = 0, z1 = ntz;
-    if (m.gtx_r) {
+    if (m.gtx.r) {
         FAMG_REQUIRE(mode != SPMV_SETDF || (epi.y2 && (epi.d || epi.dc || epi.dk != 0.0)), AMG_ERR_INVALID,
                      "SETDF needs y2 and d");
         gtx_tiles(ntz, seg, a.wz, a.kz, a.kz_lo, a.kz_hi,

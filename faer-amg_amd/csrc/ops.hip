@@ -570,7 +570,7 @@ void MultigridOp::smooth(int64_t l, double *&v, double *&t, const double *f, boo
 // residual then gathers d as randomly as x, and that doubled gather cost more
 // than the pass it saves (Q1 elasticity 1.57M rows: 640 vs 388 + 15 us).
 bool fold_level(const CsrOp *A, const DiagOp *D, const CsrOp *P, bool fold_zero_guess, bool v_zero, int64_t steps) {
-    const bool gather_cheap = A && 2 * A->m.sell_mode_slices[2] < A->m.nslices;
+    const bool gather_cheap = A && 2 * A->m.sell.mode_slices[2] < A->m.sell.nslices;
     // x-staged stencil classes (levels 1-3 of the box hierarchies): d*f can be
     // staged with the window (1-B codes of d per staged point) and the
     // correction's d*f epilogue streams dc and f in place of v, saving the
@@ -581,20 +581,20 @@ bool fold_level(const CsrOp *A, const DiagOp *D, const CsrOp *P, bool fold_zero_
     // small wave-per-row levels below, which lose 0.6 us the same way).
     const bool fold_xscs = flag(FLAG_FOLD_XSCS) != 0;
     const bool p_add0 = P && (P->m.kernel == SPMV_KERNEL_SELL || P->m.kernel == SPMV_KERNEL_SELLP ||
-                              P->m.kernel == SPMV_KERNEL_STREAM || P->m.kernel == SPMV_KERNEL_VECTOR || P->m.gtc_on);
+                              P->m.kernel == SPMV_KERNEL_STREAM || P->m.kernel == SPMV_KERNEL_VECTOR || P->m.gtc.built());
     // every fold writes the correction d*f + P v_c with P's ADD0 epilogue (the 3x3-block
     // kernel has none: a level with a block-stored P never folds)
     return fold_zero_guess && v_zero && steps == 1 && A && D && P && p_add0 &&
-                      ((A->m.kernel == SPMV_KERNEL_SELL && A->m.sell_vbits == 0 && gather_cheap) ||
+                      ((A->m.kernel == SPMV_KERNEL_SELL && A->m.sell.vbits == 0 && gather_cheap) ||
                        A->m.kernel == SPMV_KERNEL_XS ||  // x-staged: d*x staged with x, no extra gather
-                       (fold_xscs && A->m.kernel == SPMV_KERNEL_SCS && A->m.xscs && p_add0) ||
+                       (fold_xscs && A->m.kernel == SPMV_KERNEL_SCS && A->m.scs.staged && p_add0) ||
                        // wave-per-row levels small enough that x and d stay in L2 (A_4 of the
                        // box hierarchies: 4096 rows): d gathered beside x costs no HBM bytes
                        (fold_xscs && A->m.kernel == SPMV_KERNEL_VECTOR && A->m.ncols <= 65536 && p_add0) ||
                        (A->m.kernel == SPMV_KERNEL_DIA &&
                         (fold_dia_mode() == 1 ||
                          (fold_dia_mode() < 0 &&
-                          ((P->m.kernel == SPMV_KERNEL_SELL && P->m.sell_short) || P->m.gtc_on)))));
+                          ((P->m.kernel == SPMV_KERNEL_SELL && P->m.sell.is_short) || P->m.gtc.built())))));
 }
 
 // cycle (multigrid.rs:269-380).  The result ends in the buffer v points to on
@@ -1212,8 +1212,8 @@ std::shared_ptr<MultigridOp> sa_build_box(const CsrPtr &A, int64_t nx, int64_t n
                 gtc_attach(P->m, fg, cg, 0);
                 gtc_attach(R->m, fg, cg, 1);
                 // the wider classes where the 8-bit ones do not fit (levels >= 1), or everywhere (FAMG_GTX=2)
-                if (!P->m.gtc_on || gtx_mode() == 2) gtx_attach(P->m, fg, cg, 0);
-                if (!R->m.gtc_on || gtx_mode() == 2) gtx_attach(R->m, fg, cg, 1);
+                if (!P->m.gtc.built() || gtx_mode() == 2) gtx_attach(P->m, fg, cg, 0);
+                if (!R->m.gtc.built() || gtx_mode() == 2) gtx_attach(R->m, fg, cg, 1);
             }
         }
         const int64_t cgrid[3] = {ncx, ncy, ncz};  // the coarse grid (x-staged stencil kernels)

@@ -353,7 +353,7 @@ static CsrPtr csr_permuted(const CsrOp &A, const std::vector<int32_t> &rows_n2o,
     P->m.col_orig = col_n2o;
     // the copy keeps the original's kind of storage (the heuristics that chose it
     // see other rows or other slices), so every row sums in the same order
-    P->m.no_bsr = m.no_bsr || !allow_bsr || !m.has_bsr();
+    P->m.no_bsr = m.no_bsr || !allow_bsr || !m.bsr.built();
     P->m.bsr_pin = !P->m.no_bsr;
     P->m.kind_pin = (int8_t)std::min(sum_class(m), 2);  // (class 3 only in mode 2: CSR-stream)
     csr_finalize(P->m);
@@ -390,7 +390,7 @@ static bool level_reorderable(const MgLevel &L, const MgLevel *prev) {
     for (const LinOp *op : {L.R.get(), L.P.get(), prev ? prev->R.get() : nullptr, prev ? prev->P.get() : nullptr}) {
         if (!op) continue;
         auto *c = dynamic_cast<const CsrOp *>(op);
-        if (!c || c->m.gtc_on || c->m.gtx_on || c->m.kernel == SPMV_KERNEL_SELLP) return false;
+        if (!c || c->m.gtc.built() || c->m.gtx.built() || c->m.kernel == SPMV_KERNEL_SELLP) return false;
     }
     return true;
 }
@@ -444,7 +444,7 @@ void MultigridOp::reorder_levels() {
         if (reorder == 1 && !level_bitwise(levels[l], l > 0 ? &levels[l - 1] : nullptr)) continue;
         const GpuCsr &m = dynamic_cast<CsrOp *>(levels[l].A.get())->m;
         const int64_t n = m.nrows;
-        const int bs = m.has_bsr() ? 3 : 1;
+        const int bs = m.bsr.built() ? 3 : 1;
         std::vector<int64_t> rp(n + 1);
         std::vector<int32_t> col(std::max<int64_t>(1, m.nnz));
         FAMG_CHECK_HIP(hipMemcpyAsync(rp.data(), m.rp64.get(), (n + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -518,7 +518,7 @@ void MultigridOp::reorder_levels() {
                 if (!pr.first) continue;
                 const GpuCsr &a = dynamic_cast<CsrOp *>(pr.first.get())->m;
                 const GpuCsr &b = dynamic_cast<CsrOp *>(pr.second.get())->m;
-                same = same && a.kernel == b.kernel && a.has_bsr() == b.has_bsr() && sum_class(a) <= 2;
+                same = same && a.kernel == b.kernel && a.bsr.built() == b.bsr.built() && sum_class(a) <= 2;
             }
         if (!same) {
             undo_reorder();

@@ -491,20 +491,6 @@ static bool scs_disabled() {
     return off;
 }
 
-void scs_release(GpuCsr &m) {
-    m.scs_cls.release();
-    m.scs_dict.release();
-    m.scs_offs.release();
-    m.scs_k = m.scs_nclass = m.scs_ib = 0;
-    m.scs_kr = 0;
-    m.scs_seg = -1;
-    m.scs_lanes = false;
-    m.xscs = false;
-    m.xscs_tile_src = 0;
-    m.xscs_split = false;
-    m.xscs_lo.release();
-}
-
 // A/B switch FAMG_XSCS=0: no x-staged stencil classes; FAMG_XSCS_TILE=tx,ty,tz
 // forces the tile
 static bool xscs_enabled() {
@@ -518,18 +504,18 @@ static bool xscs_split_enabled() { return env_not_zero("FAMG_XSCS_SPLIT"); }
 
 // LDS the eight-lanes-per-row kernel keeps behind the window: its k window offsets
 // (tiles and window strides are chosen to leave that room within 64 KB)
-static int64_t xscs_lo_bytes(const GpuCsr &m, int k) { return m.xscs_split ? (int64_t)k * 4 : 0; }
+static int64_t xscs_lo_bytes(const GpuCsr &m, int k) { return m.scs.xsplit ? (int64_t)k * 4 : 0; }
 
 // LDS of the x-staged kernels for m's tile
 static size_t xscs_lds(const GpuCsr &m) {
-    const size_t win = (size_t)m.xscs_ws * (m.xscs_t[1] + 2 * m.xscs_r[1]) * (m.xscs_t[2] + 2 * m.xscs_r[2]) * sizeof(double);
-    return win + (size_t)xscs_lo_bytes(m, (int)m.scs_k);
+    const size_t win = (size_t)m.scs.xws * (m.scs.xt[1] + 2 * m.scs.xr[1]) * (m.scs.xt[2] + 2 * m.scs.xr[2]) * sizeof(double);
+    return win + (size_t)xscs_lo_bytes(m, (int)m.scs.k);
 }
 
 // the eight-lanes-per-row kernel takes m's launches
-static bool xscs_takes_split(const GpuCsr &m) { return m.xscs && m.xscs_split; }
+static bool xscs_takes_split(const GpuCsr &m) { return m.scs.staged && m.scs.xsplit; }
 
-int xscs_row_lanes(const GpuCsr &m) { return m.has_scs() && xscs_takes_split(m) ? XSPLIT_LANES : 1; }
+int xscs_row_lanes(const GpuCsr &m) { return m.scs.built() && xscs_takes_split(m) ? XSPLIT_LANES : 1; }
 
 // The grid hint applies to the whole square matrix.
 static bool grid_applies(const GpuCsr &m) {
@@ -569,28 +555,28 @@ static int xscs_stride(const int *t, int wx, int wy, int wz, int64_t rsv) {
 }
 
 static void xscs_set_tile(GpuCsr &m, const int *t) {
-    const int rx = m.xscs_r[0], ry = m.xscs_r[1], rz = m.xscs_r[2];
+    const int rx = m.scs.xr[0], ry = m.scs.xr[1], rz = m.scs.xr[2];
     const int wx = t[0] + 2 * rx, wy = t[1] + 2 * ry;
-    const int Kp = (int)(m.xscs_steps.size() / 3);
+    const int Kp = (int)(m.scs.xsteps.size() / 3);
     const int ws = xscs_stride(t, wx, wy, t[2] + 2 * rz, xscs_lo_bytes(m, Kp));
     std::vector<int32_t> lo(Kp);
     for (int k = 0; k < Kp; k++)
-        lo[k] = (m.xscs_steps[3 * k + 2] * wy + m.xscs_steps[3 * k + 1]) * ws + m.xscs_steps[3 * k];
-    m.xscs_ws = ws;
-    m.xscs_lo.resize(Kp);
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.xscs_lo.get(), lo.data(), Kp * 4, hipMemcpyHostToDevice, m.ctx->stream));
+        lo[k] = (m.scs.xsteps[3 * k + 2] * wy + m.scs.xsteps[3 * k + 1]) * ws + m.scs.xsteps[3 * k];
+    m.scs.xws = ws;
+    m.scs.xlo.resize(Kp);
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.scs.xlo.get(), lo.data(), Kp * 4, hipMemcpyHostToDevice, m.ctx->stream));
     FAMG_CHECK_HIP(hipStreamSynchronize(m.ctx->stream));
-    for (int q = 0; q < 3; q++) m.xscs_t[q] = t[q];
+    for (int q = 0; q < 3; q++) m.scs.xt[q] = t[q];
     // the staging loops divide by the window and tile extents through float
     // reciprocals: checked once here, at storage build, not per launch
     const int wz = t[2] + 2 * rz;
-    m.xscs_fdiv = fdiv_exact(wx * wy * wz, wx, 1.0f / (float)wx) && fdiv_exact(wy * wz, wy, 1.0f / (float)wy) &&
+    m.scs.xfdiv = fdiv_exact(wx * wy * wz, wx, 1.0f / (float)wx) && fdiv_exact(wy * wz, wy, 1.0f / (float)wy) &&
                   fdiv_exact(1024, t[0], 1.0f / (float)t[0]) && fdiv_exact(1024 / t[0] + 1, t[1], 1.0f / (float)t[1]);
 }
 
 // Decompose the offsets into grid steps (dx, dy, dz) (centred residues), check
 // that every nonzero entry's step stays inside the grid, pick the tile and store
-// the window offsets: m.xscs on success.
+// the window offsets: m.scs.staged on success.
 static bool xscs_setup(GpuCsr &m, const std::vector<int32_t> &offs, int Kp, const std::vector<int64_t> &rp,
                        const std::vector<int32_t> &col, const std::vector<double> &val) {
     const int64_t nx = m.grid[0], ny = m.grid[1], nz = m.grid[2], pl = nx * ny, n = m.nrows;
@@ -669,14 +655,14 @@ static bool xscs_setup(GpuCsr &m, const std::vector<int32_t> &offs, int Kp, cons
         }
     }
     if (!best[0]) return false;
-    m.xscs_steps.assign(3 * Kp, 0);  // padding offsets: the row itself
+    m.scs.xsteps.assign(3 * Kp, 0);  // padding offsets: the row itself
     for (int k = 0; k < K; k++) {
-        m.xscs_steps[3 * k] = dx[k];
-        m.xscs_steps[3 * k + 1] = dy[k];
-        m.xscs_steps[3 * k + 2] = dz[k];
+        m.scs.xsteps[3 * k] = dx[k];
+        m.scs.xsteps[3 * k + 1] = dy[k];
+        m.scs.xsteps[3 * k + 2] = dz[k];
     }
-    m.xscs_r[0] = rx; m.xscs_r[1] = ry; m.xscs_r[2] = rz;
-    m.xscs = true;
+    m.scs.xr[0] = rx; m.scs.xr[1] = ry; m.scs.xr[2] = rz;
+    m.scs.staged = true;
     xscs_set_tile(m, best);
     return true;
 }
@@ -739,18 +725,18 @@ static void spmv_xscs(const GpuCsr &m, const double *x, double *y, SpmvMode mode
 // tile changes no result (same sums in the same order).
 static void xscs_autotune(GpuCsr &m) {
     if (env_char("FAMG_XSCS_TILE") >= 0) {
-        m.xscs_tile_src = TUNE_ENV;
+        m.scs.xtile_src = TUNE_ENV;
         return;
     }
     const int64_t nx = m.grid[0], ny = m.grid[1], nz = m.grid[2], n = m.nrows;
-    const int rx = m.xscs_r[0], ry = m.xscs_r[1], rz = m.xscs_r[2];
+    const int rx = m.scs.xr[0], ry = m.scs.xr[1], rz = m.scs.xr[2];
     // a shape of the frozen table (tuning.cpp) takes its tile without timing
-    const TileKey key{nx, ny, nz, rx, ry, rz, (int)m.scs_kr, m.scs_nclass, m.rframe.on()};
+    const TileKey key{nx, ny, nz, rx, ry, rz, (int)m.scs.kr, m.scs.nclass, m.rframe.on()};
     {
         int t[3];
         if (env_char("FAMG_TUNE_RETIME") < 0 && tune_tile_lookup(key, t)) {
             xscs_set_tile(m, t);
-            m.xscs_tile_src = TUNE_TABLE;
+            m.scs.xtile_src = TUNE_TABLE;
             tune_tile_record(key, t, TUNE_TABLE);
             return;
         }
@@ -762,7 +748,7 @@ static void xscs_autotune(GpuCsr &m) {
                 if (tx > nx || ty > ny || tz > nz) continue;
                 const int64_t T = (int64_t)tx * ty * tz;
                 const int64_t W = (int64_t)(tx + 2 * rx) * (ty + 2 * ry) * (tz + 2 * rz);
-                if (T < std::min<int64_t>(64, n) || T > 1024 || W * 8 + xscs_lo_bytes(m, (int)m.scs_k) > 64 * 1024) continue;
+                if (T < std::min<int64_t>(64, n) || T > 1024 || W * 8 + xscs_lo_bytes(m, (int)m.scs.k) > 64 * 1024) continue;
                 if (T < 128 && n >= 1024 * 256) continue;
                 if (tx < 8 && nx >= 8) continue;  // short x rows stage poorly (ab_xscs)
                 cands.push_back({tx, ty, tz});
@@ -774,7 +760,7 @@ static void xscs_autotune(GpuCsr &m) {
     hipEvent_t e0, e1;
     FAMG_CHECK_HIP(hipEventCreate(&e0));
     FAMG_CHECK_HIP(hipEventCreate(&e1));
-    int best[3] = {m.xscs_t[0], m.xscs_t[1], m.xscs_t[2]};
+    int best[3] = {m.scs.xt[0], m.scs.xt[1], m.scs.xt[2]};
     float best_ms = 1e30f;
     for (const auto &c : cands) {
         xscs_set_tile(m, c.data());
@@ -793,12 +779,11 @@ static void xscs_autotune(GpuCsr &m) {
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     xscs_set_tile(m, best);
-    m.xscs_tile_src = TUNE_TIMED;
+    m.scs.xtile_src = TUNE_TIMED;
     tune_tile_record(key, best, TUNE_TIMED);
 }
 
 bool build_scs(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes) {
-    scs_release(m);
     if (g_spmv_format_policy != 0 || scs_disabled() || m.no_sellp || m.nrows < 1024 || m.nnz == 0 ||
         m.ncols < m.nrows)
         return false;
@@ -822,7 +807,7 @@ bool build_scs(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes) {
             if (m.seg_rows[g + 1] - m.seg_rows[g] > m.seg_rows[seg + 1] - m.seg_rows[seg]) seg = (int64_t)g;
         r0 = m.seg_rows[seg];
         r1 = m.seg_rows[seg + 1];
-        if (r1 - r0 < 1024 || (m.has_dia() && m.dia_seg == seg)) return false;
+        if (r1 - r0 < 1024 || (m.dia.built() && m.dia.seg == seg)) return false;
         other_bytes = (int64_t)((double)other_bytes * (double)(r1 - r0) / (double)n);
     }
     hipStream_t st = m.ctx->stream;
@@ -898,14 +883,14 @@ bool build_scs(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes) {
     const bool rows_pref = scs_rows_pref() && r1 - r0 < SCS_LANES_ROWS && Kp >= 256 && !framed;
     // few long rows, the rule of the wave-per-row class kernel: x-staged with eight
     // lanes per row (set first: the tile must leave LDS for the window offsets)
-    m.xscs_split = ib == 2 && r1 - r0 < SCS_LANES_ROWS && Kp >= 256 && xscs_split_enabled();
+    m.scs.xsplit = ib == 2 && r1 - r0 < SCS_LANES_ROWS && Kp >= 256 && xscs_split_enabled();
     const bool xs3 = !rows_pref && on_grid && dict_bytes <= (int64_t(256) << 20) &&
                      (framed || (double)stream <= 0.5 * (double)other_bytes) && xscs_setup(m, offs, Kp, rp, col, val);
-    m.xscs_split = m.xscs_split && xs3;
+    m.scs.xsplit = m.scs.xsplit && xs3;
     if (!xs3 && (K < SCS_KMIN || small_table || framed)) return false;
     // few long rows: one row per wave, the dictionary streamed (up to 256 MiB)
     const bool lanes = !xs3 && r1 - r0 < SCS_LANES_ROWS && Kp >= 256;
-    if (lanes && !scs_lanes_enabled()) { scs_release(m); return false; }
+    if (lanes && !scs_lanes_enabled()) { m.scs = {}; return false; }
     if (!xs3 && (dict_bytes > (int64_t(lanes ? 256 : 16) << 20) || (double)stream > 0.5 * (double)other_bytes))
         return false;
     std::vector<double> dict((size_t)Kp * C, 0.0);
@@ -918,49 +903,49 @@ bool build_scs(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes) {
         }
     }
     offs.resize(Kp, 0);  // padding offsets: value +0.0 at the row itself
-    m.scs_offs.resize(Kp);
-    m.scs_dict.resize((size_t)Kp * C);
-    m.scs_cls.resize(n * ib);
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.scs_offs.get(), offs.data(), Kp * 4, hipMemcpyHostToDevice, st));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.scs_dict.get(), dict.data(), dict.size() * 8, hipMemcpyHostToDevice, st));
+    m.scs.offs.resize(Kp);
+    m.scs.dict.resize((size_t)Kp * C);
+    m.scs.cls.resize(n * ib);
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.scs.offs.get(), offs.data(), Kp * 4, hipMemcpyHostToDevice, st));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.scs.dict.get(), dict.data(), dict.size() * 8, hipMemcpyHostToDevice, st));
     if (ib == 1) {
         std::vector<uint8_t> c8(n);
         for (int64_t i = 0; i < n; i++) c8[i] = (uint8_t)cls[i];
-        FAMG_CHECK_HIP(hipMemcpyAsync(m.scs_cls.get(), c8.data(), n, hipMemcpyHostToDevice, st));
+        FAMG_CHECK_HIP(hipMemcpyAsync(m.scs.cls.get(), c8.data(), n, hipMemcpyHostToDevice, st));
         FAMG_CHECK_HIP(hipStreamSynchronize(st));
     } else {
-        FAMG_CHECK_HIP(hipMemcpyAsync(m.scs_cls.get(), cls.data(), n * 2, hipMemcpyHostToDevice, st));
+        FAMG_CHECK_HIP(hipMemcpyAsync(m.scs.cls.get(), cls.data(), n * 2, hipMemcpyHostToDevice, st));
         FAMG_CHECK_HIP(hipStreamSynchronize(st));
     }
-    m.scs_k = Kp;
-    m.scs_kr = K;
-    m.scs_nclass = C;
-    m.scs_ib = ib;
-    m.scs_seg = seg;
-    m.scs_lanes = lanes;
-    if (m.xscs) xscs_autotune(m);
+    m.scs.k = Kp;
+    m.scs.kr = K;
+    m.scs.nclass = C;
+    m.scs.ib = ib;
+    m.scs.seg = seg;
+    m.scs.lanes = lanes;
+    if (m.scs.staged) xscs_autotune(m);
     return true;
 }
 
 static void spmv_xscs(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi,
                       hipStream_t s, int64_t seg) {
     XscsArgs a{};
-    a.cls = m.scs_cls.get();
-    a.dict = m.scs_dict.get();
-    a.lo = m.xscs_lo.get();
-    a.k = (int32_t)m.scs_k;
-    a.kr = (int32_t)m.scs_kr;
+    a.cls = m.scs.cls.get();
+    a.dict = m.scs.dict.get();
+    a.lo = m.scs.xlo.get();
+    a.k = (int32_t)m.scs.k;
+    a.kr = (int32_t)m.scs.kr;
     a.nx = (int)m.grid[0]; a.ny = (int)m.grid[1]; a.nz = (int)m.grid[2];
-    a.tx = m.xscs_t[0]; a.ty = m.xscs_t[1]; a.tz = m.xscs_t[2];
-    a.rx = m.xscs_r[0]; a.ry = m.xscs_r[1]; a.rz = m.xscs_r[2];
+    a.tx = m.scs.xt[0]; a.ty = m.scs.xt[1]; a.tz = m.scs.xt[2];
+    a.rx = m.scs.xr[0]; a.ry = m.scs.xr[1]; a.rz = m.scs.xr[2];
     a.wx = a.tx + 2 * a.rx; a.wy = a.ty + 2 * a.ry; a.wz = a.tz + 2 * a.rz;
-    a.ws = m.xscs_ws;
+    a.ws = m.scs.xws;
     FAMG_REQUIRE(a.ws >= a.wx, AMG_ERR_UNSUPPORTED, "x-staged classes: no window stride");
     a.ntx = (int)ceil_div(a.nx, a.tx); a.nty = (int)ceil_div(a.ny, a.ty);
     const int ntz = (int)ceil_div(a.nz, a.tz);
     a.rwx = 1.0f / (float)a.wx; a.rwy = 1.0f / (float)a.wy;
     a.rtx = 1.0f / (float)a.tx; a.rty = 1.0f / (float)a.ty;
-    FAMG_REQUIRE(m.xscs_fdiv, AMG_ERR_UNSUPPORTED, "x-staged classes: window too large for the float divisions");
+    FAMG_REQUIRE(m.scs.xfdiv, AMG_ERR_UNSUPPORTED, "x-staged classes: window too large for the float divisions");
     a.zlo = 0; a.zhi = a.nz; a.add_lo = a.add_hi = 0;
     const SlabFrame &F = m.cframe;
     if (F.on()) {  // rank-local: the ghost planes below / above the owned ones
@@ -1019,7 +1004,7 @@ static void spmv_xscs(const GpuCsr &m, const double *x, double *y, SpmvMode mode
     case SPMV_JACOBI: FAMG_XS3(SPMV_JACOBI, IB) break;                                             \
     default: fail(AMG_ERR_UNSUPPORTED, "stencil-class storage: unsupported SpMV epilogue");        \
     }
-    if (m.scs_ib == 1) { FAMG_XS3M(1) }
+    if (m.scs.ib == 1) { FAMG_XS3M(1) }
     else { FAMG_XS3M(2) }
 #undef FAMG_XS3M
 #undef FAMG_XS3
@@ -1027,7 +1012,7 @@ static void spmv_xscs(const GpuCsr &m, const double *x, double *y, SpmvMode mode
 }
 
 // the x-staged kernel takes the launch (a framed matrix: segments are z-tile ranges, not row ranges)
-bool scs_takes_xscs(const GpuCsr &m, int64_t seg) { return m.xscs && (seg < 0 || m.cframe.on()); }
+bool scs_takes_xscs(const GpuCsr &m, int64_t seg) { return m.scs.staged && (seg < 0 || m.cframe.on()); }
 
 void spmv_scs(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
               int64_t seg) {
@@ -1038,11 +1023,11 @@ void spmv_scs(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
     const int64_t r0 = seg < 0 ? 0 : m.seg_rows[seg];
     const int64_t r1 = seg < 0 ? m.nrows : m.seg_rows[seg + 1];
     if (r1 <= r0) return;
-    ScsArgs a{m.scs_cls.get(), m.scs_dict.get(), m.scs_offs.get(), (int32_t)m.scs_k, (int32_t)m.scs_nclass,
+    ScsArgs a{m.scs.cls.get(), m.scs.dict.get(), m.scs.offs.get(), (int32_t)m.scs.k, (int32_t)m.scs.nclass,
               (int32_t)r0, (int32_t)r1, (int32_t)m.ncols, x, y, epi.b, epi.d, epi.dc, epi.dt};
-    const dim3 grid((unsigned)ceil_div(r1 - r0, m.scs_lanes ? 4 : 512)), block(256);
+    const dim3 grid((unsigned)ceil_div(r1 - r0, m.scs.lanes ? 4 : 512)), block(256);
 #define FAMG_SCS2(M, IB)                                                                           \
-    if (m.scs_lanes) spmv_scs_lanes_kernel<M, IB><<<grid, block, 0, s>>>(a);                       \
+    if (m.scs.lanes) spmv_scs_lanes_kernel<M, IB><<<grid, block, 0, s>>>(a);                       \
     else spmv_scs_kernel<M, IB><<<grid, block, 0, s>>>(a);
 #define FAMG_SCS(IB)                                                                               \
     switch (mode) {                                                                                \
@@ -1052,7 +1037,7 @@ void spmv_scs(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
     case SPMV_JACOBI: FAMG_SCS2(SPMV_JACOBI, IB) break;                                            \
     default: fail(AMG_ERR_UNSUPPORTED, "stencil-class storage: unsupported SpMV epilogue");        \
     }
-    if (m.scs_ib == 1) { FAMG_SCS(1) }
+    if (m.scs.ib == 1) { FAMG_SCS(1) }
     else { FAMG_SCS(2) }
 #undef FAMG_SCS
 #undef FAMG_SCS2

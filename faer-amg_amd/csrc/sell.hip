@@ -17,7 +17,7 @@ constexpr int64_t SELL_PAIR_MIN_SLICES = 1;  // pairing paid on every level meas
 // ------------------------------------------------------------------- SELL-64
 //
 // Slice s = up to 64 consecutive rows, one lane per row, w_s entry steps.  The
-// slice's block in sell_data is [w_s x 64 fp64 values | column block], the
+// slice's block in sell.data is [w_s x 64 fp64 values | column block], the
 // column of lane l at step t given by the slice's column mode:
 //   0 implicit  col = base[t] + l                    (0 B/entry)
 //   1 u16       col = base[t] + d16(t, l)            (2 B/entry)
@@ -36,7 +36,7 @@ constexpr int64_t SELL_PAIR_MIN_SLICES = 1;  // pairing paid on every level meas
 // two steps (4 B / 8 B for two compressed columns); an odd last step is stored
 // plainly at t*64 + l.  Streamed with 8-B non-temporal loads the values ran at
 // roughly 0.54-0.70x the 16-B rate (MI355X_MICROARCH.md, L2-served loads).
-// `sell_paired = false` keeps one 512-B row per step (A/B switch,
+// `sell.paired = false` keeps one 512-B row per step (A/B switch,
 // FAMG_SELL_LAYOUT=step at build time).
 constexpr int SELL_VAL_STEP = SELL_C * 8;  // bytes of values per step
 
@@ -58,7 +58,7 @@ struct SellArgs {
     int32_t spw;  // slices per wave (value codes: 2 on large matrices, else 1)
 };
 
-// ---- one step per 512-B row (sell_paired = false)
+// ---- one step per 512-B row (sell.paired = false)
 
 template <int MODE, int CM, int U>
 __device__ __forceinline__ void sell_chunk(const double *__restrict__ v, const void *__restrict__ ix,
@@ -106,7 +106,7 @@ __device__ __forceinline__ double sell_walk_steps(const char *blkp, const int32_
     return acc;
 }
 
-// ---- step pairs (sell_paired = true)
+// ---- step pairs (sell.paired = true)
 
 // UP step pairs starting at pair p0, plus the odd last step when TAIL; every
 // load of the group is issued before the dependent x gathers, and the row sum
@@ -174,7 +174,7 @@ __device__ __forceinline__ double sell_walk_pairs(const char *blkp, const int32_
     return acc;
 }
 
-// ---- value codes (sell_vbits = 4, 8 or 16)
+// ---- value codes (sell.vbits = 4, 8 or 16)
 //
 // A matrix whose stored values take at most 16 / 256 / 65536 distinct fp64 bit
 // patterns (the padding's +0.0 included) stores a 4 / 8 / 16-bit code per
@@ -938,24 +938,6 @@ __global__ __launch_bounds__(256) void k_sell_fill(const int64_t *rp, const int3
 }
 
 void build_sell(GpuCsr &m, const std::vector<int64_t> &rp) {
-    m.sell_row0.release();
-    m.sell_soff.release();
-    m.sell_desc.release();
-    m.sell_base.release();
-    m.sell_data.release();
-    m.sell_vtab.release();
-    m.dia_codes.release();
-    m.dia_vtab.release();
-    m.dia_ntab = 0;
-    m.dia_k = m.dia_cw = m.dia_vbits = m.dia_pat = 0;
-    m.dia_r0 = m.dia_r1 = m.dia_seg = 0;
-    m.dia_rowid = nullptr;
-    m.dia_off.clear();
-    m.nslices = m.sell_steps = m.sell_bytes = m.sell_ntab = 0;
-    m.sell_vbits = 0;
-    m.sell_mode_slices[0] = m.sell_mode_slices[1] = m.sell_mode_slices[2] = 0;
-    m.sell_short = false;
-    m.seg_slc.clear();
     const int pol = g_spmv_format_policy;
     if (pol == 1 || pol == 3 || m.kind_pin >= 1 || m.nrows == 0 || m.nnz == 0) return;
     // slices never straddle a segment
@@ -980,8 +962,8 @@ void build_sell(GpuCsr &m, const std::vector<int64_t> &rp) {
         if (m.seg_rows[g + 1] - m.seg_rows[g] > m.seg_rows[dseg + 1] - m.seg_rows[dseg]) dseg = (int64_t)g;
     // (a renumbered copy, reorder.hip, keeps its rows' stored order: no DIA, no aligned slices)
     if (!m.order_fixed && build_dia(m, vb, tab, rp, m.seg_rows[dseg], m.seg_rows[dseg + 1])) {
-        m.dia_seg = dseg;
-        if (m.dia_r0 == 0 && m.dia_r1 == m.nrows) return;
+        m.dia.seg = dseg;
+        if (m.dia.r0 == 0 && m.dia.r1 == m.nrows) return;
     }
     hipStream_t s = m.ctx->stream;
     DevBuf<int32_t> drow0(ns + 1), dplan(4 * ns);
@@ -1016,35 +998,35 @@ void build_sell(GpuCsr &m, const std::vector<int64_t> &rp) {
     const bool ok = pol == 2 || m.kind_pin == 0 || (bytes * 100 <= 12 * m.nnz * 125 && (m.nrows >= SELL_MIN_ROWS || maxlen <= 16) &&
                                  (vec_min_avg() >= VECTOR_MIN_AVG || m.nnz < vec_min_avg() * m.nrows));
     if (!ok) return;
-    m.sell_row0 = std::move(drow0);
-    m.sell_soff.resize(ns + 1);
-    m.sell_desc.resize(ns);
-    m.sell_base.resize(std::max<int64_t>(1, steps));
-    m.sell_data.resize(std::max<int64_t>(128, bytes));
+    m.sell.row0 = std::move(drow0);
+    m.sell.soff.resize(ns + 1);
+    m.sell.desc.resize(ns);
+    m.sell.base.resize(std::max<int64_t>(1, steps));
+    m.sell.data.resize(std::max<int64_t>(128, bytes));
     DevBuf<uint8_t> dal(ns);
     const char *lay = getenv("FAMG_SELL_LAYOUT");
-    m.sell_paired = !(lay && std::string(lay) == "step");
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.sell_soff.get(), soff.data(), (ns + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.sell_desc.get(), desc.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    m.sell.paired = !(lay && std::string(lay) == "step");
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.sell.soff.get(), soff.data(), (ns + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.sell.desc.get(), desc.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     FAMG_CHECK_HIP(hipMemcpyAsync(dal.get(), aligned.data(), ns, hipMemcpyHostToDevice, s));
     if (vb) {
-        m.sell_vtab.resize(tab.size());
-        FAMG_CHECK_HIP(hipMemcpyAsync(m.sell_vtab.get(), tab.data(), tab.size() * sizeof(double),
+        m.sell.vtab.resize(tab.size());
+        FAMG_CHECK_HIP(hipMemcpyAsync(m.sell.vtab.get(), tab.data(), tab.size() * sizeof(double),
                                       hipMemcpyHostToDevice, s));
     }
     hipLaunchKernelGGL(k_sell_fill, grid, dim3(256), 0, s, m.rp64.get(), m.col.get(), m.val.get(),
-                       m.sell_row0.get(), m.sell_soff.get(), m.sell_desc.get(), dal.get(), ns, m.ncols,
-                       m.sell_paired, vb, reinterpret_cast<const unsigned long long *>(m.sell_vtab.get()),
-                       (int)tab.size(), m.sell_base.get(), m.sell_data.get());
+                       m.sell.row0.get(), m.sell.soff.get(), m.sell.desc.get(), dal.get(), ns, m.ncols,
+                       m.sell.paired, vb, reinterpret_cast<const unsigned long long *>(m.sell.vtab.get()),
+                       (int)tab.size(), m.sell.base.get(), m.sell.data.get());
     FAMG_CHECK_HIP(hipGetLastError());
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
-    m.nslices = ns;
-    m.sell_steps = steps;
-    m.sell_bytes = bytes;
-    m.sell_vbits = vb;
-    m.sell_ntab = vb ? (int64_t)tab.size() : 0;
-    for (int k = 0; k < 3; k++) m.sell_mode_slices[k] = cnt[k];
-    m.seg_slc = seg_slc;
+    m.sell.nslices = ns;
+    m.sell.steps = steps;
+    m.sell.bytes = bytes;
+    m.sell.vbits = vb;
+    m.sell.ntab = vb ? (int64_t)tab.size() : 0;
+    for (int k = 0; k < 3; k++) m.sell.mode_slices[k] = cnt[k];
+    m.sell.seg_slc = seg_slc;
     // short slices (coded, <= 4 steps, implicit / u16 columns, pairs of equal
     // width and column mode, one row segment): spmv_sell_short_kernel
     bool sh = vb != 0 && ns % 2 == 0 && cnt[2] == 0 && m.seg_rows.size() == 2;
@@ -1052,45 +1034,45 @@ void build_sell(GpuCsr &m, const std::vector<int64_t> &rp) {
         const int32_t wa = soff[k + 1] - soff[k], wb = soff[k + 2] - soff[k + 1];
         sh = wa <= 4 && wa == wb && (desc[k] >> 30) == (desc[k + 1] >> 30) && row0[k + 1] - row0[k] == 64;
     }
-    m.sell_short = sh;
+    m.sell.is_short = sh;
 }
 
 // A/B switch FAMG_SELL_SHORT=0: short-slice operators take the generic SELL kernel
 bool sell_takes_short(const GpuCsr &m, SpmvMode mode, int64_t seg) {
     static const bool enabled = env_not_zero("FAMG_SELL_SHORT");
-    return m.sell_short && seg < 0 && mode != SPMV_SGS && mode != SPMV_RESID0 && enabled;
+    return m.sell.is_short && seg < 0 && mode != SPMV_SGS && mode != SPMV_RESID0 && enabled;
 }
 
 void spmv_sell(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
                const SpmvRoute &r) {
-    const int64_t s0 = r.seg < 0 ? 0 : m.seg_slc[r.seg];
-    const int64_t s1 = r.seg < 0 ? m.nslices : m.seg_slc[r.seg + 1];
+    const int64_t s0 = r.seg < 0 ? 0 : m.sell.seg_slc[r.seg];
+    const int64_t s1 = r.seg < 0 ? m.sell.nslices : m.sell.seg_slc[r.seg + 1];
     if (s1 <= s0) return;
-    SellArgs a{m.sell_row0.get(), m.sell_soff.get(), m.sell_desc.get(), m.sell_base.get(),
-               m.sell_data.get(), (int32_t)s0, (int32_t)(s1 - s0), Epi{x, y, epi.b, epi.d, epi.perm, epi.dc, epi.dt, epi.dk},
-               m.sell_vtab.get(), (int32_t)m.sell_ntab, 1};
+    SellArgs a{m.sell.row0.get(), m.sell.soff.get(), m.sell.desc.get(), m.sell.base.get(),
+               m.sell.data.get(), (int32_t)s0, (int32_t)(s1 - s0), Epi{x, y, epi.b, epi.d, epi.perm, epi.dc, epi.dt, epi.dk},
+               m.sell.vtab.get(), (int32_t)m.sell.ntab, 1};
     // value codes: two slices per wave when there are enough waves to fill the chip twice over
-    const int lay = m.sell_vbits ? 4 : 0;
+    const int lay = m.sell.vbits ? 4 : 0;
     if (sell_slices_per_wave(lay, mode) == 2 && s1 - s0 >= SELL_PAIR_MIN_SLICES) a.spw = 2;
     const dim3 grid((unsigned)ceil_div(s1 - s0, 4 * a.spw * sell_groups_per_wave(lay))), block(256);
     if (r.sell_short) {
         const dim3 g2((unsigned)ceil_div(s1 - s0, 8));
-        if (m.sell_vbits == 4) {
+        if (m.sell.vbits == 4) {
             FAMG_LAUNCH_MODES(spmv_sell_short_kernel, g2, block, s, a, FAMG_LAY4)
-        } else if (m.sell_vbits == 8) {
+        } else if (m.sell.vbits == 8) {
             FAMG_LAUNCH_MODES(spmv_sell_short_kernel, g2, block, s, a, FAMG_LAY8)
         } else {
             FAMG_LAUNCH_MODES(spmv_sell_short_kernel, g2, block, s, a, FAMG_LAY16)
         }
-    } else if (m.sell_vbits == 4) {
+    } else if (m.sell.vbits == 4) {
         FAMG_LAUNCH_MODES(spmv_sell_kernel, grid, block, s, a, FAMG_LAY4)
-    } else if (m.sell_vbits == 8) {
+    } else if (m.sell.vbits == 8) {
         FAMG_LAUNCH_MODES(spmv_sell_kernel, grid, block, s, a, FAMG_LAY8)
-    } else if (m.sell_vbits == 16 && m.sell_ntab <= 8192 && mode != SPMV_SGS &&
+    } else if (m.sell.vbits == 16 && m.sell.ntab <= 8192 && mode != SPMV_SGS &&
                ((sell_t16_mode() < 0 && m.nnz >= 32 * m.nrows) || sell_t16_mode() > 0)) {
         const int nvb = (int)grid.x;
         const dim3 g2((unsigned)(sell_t16_mode() > 0 ? std::min(nvb, 256 * sell_t16_mode()) : nvb));
-        const size_t lds = (size_t)m.sell_ntab * sizeof(double);
+        const size_t lds = (size_t)m.sell.ntab * sizeof(double);
         switch (mode) {
         case SPMV_SET: spmv_sell_t16_kernel<SPMV_SET><<<g2, block, lds, s>>>(a, nvb); break;
         case SPMV_ADD: spmv_sell_t16_kernel<SPMV_ADD><<<g2, block, lds, s>>>(a, nvb); break;
@@ -1100,9 +1082,9 @@ void spmv_sell(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const
         case SPMV_ADD0: spmv_sell_t16_kernel<SPMV_ADD0><<<g2, block, lds, s>>>(a, nvb); break;
         default: break;
         }
-    } else if (m.sell_vbits == 16) {
+    } else if (m.sell.vbits == 16) {
         FAMG_LAUNCH_MODES(spmv_sell_kernel, grid, block, s, a, FAMG_LAY16)
-    } else if (m.sell_paired) {
+    } else if (m.sell.paired) {
         FAMG_LAUNCH_MODES(spmv_sell_kernel, grid, block, s, a, FAMG_LAY1)
     } else {
         FAMG_LAUNCH_MODES(spmv_sell_kernel, grid, block, s, a, FAMG_LAY0)
@@ -1141,17 +1123,17 @@ __global__ __launch_bounds__(256) void spmm_sell_coded_kernel(SellArgs a, int kb
 
 void spmm_sell_coded(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, SpmvMode mode,
                      const SpmmEpi &epi, hipStream_t s) {
-    if (m.nslices == 0) return;
+    if (m.sell.nslices == 0) return;
     const int lay = 4;  // (what spmv_sell passes for every coded layout)
     const dim3 block(256);
     for (int64_t c0 = 0; c0 < k; c0 += SPMM_KB) {
         const int kb = (int)std::min<int64_t>(SPMM_KB, k - c0);
-        SellArgs a{m.sell_row0.get(), m.sell_soff.get(), m.sell_desc.get(), m.sell_base.get(), m.sell_data.get(), 0,
-                   (int32_t)m.nslices,
+        SellArgs a{m.sell.row0.get(), m.sell.soff.get(), m.sell.desc.get(), m.sell.base.get(), m.sell.data.get(), 0,
+                   (int32_t)m.sell.nslices,
                    Epi{x + c0 * ldx, y + c0 * ldy, epi.b ? epi.b + c0 * epi.ldb : nullptr, epi.d, nullptr, nullptr, nullptr, 0.0},
-                   m.sell_vtab.get(), (int32_t)m.sell_ntab, 1};
-        if (sell_slices_per_wave(lay, mode) == 2 && m.nslices >= SELL_PAIR_MIN_SLICES) a.spw = 2;
-        const dim3 grid((unsigned)ceil_div(m.nslices, 4 * a.spw * sell_groups_per_wave(lay)));
+                   m.sell.vtab.get(), (int32_t)m.sell.ntab, 1};
+        if (sell_slices_per_wave(lay, mode) == 2 && m.sell.nslices >= SELL_PAIR_MIN_SLICES) a.spw = 2;
+        const dim3 grid((unsigned)ceil_div(m.sell.nslices, 4 * a.spw * sell_groups_per_wave(lay)));
 #define FAMG_SELLC(LAY)                                                                                      \
     switch (mode) {                                                                                        \
     case SPMV_SET: spmm_sell_coded_kernel<SPMV_SET, LAY><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break;     \
@@ -1159,8 +1141,8 @@ void spmm_sell_coded(const GpuCsr &m, const double *x, int64_t ldx, double *y, i
     case SPMV_RESID: spmm_sell_coded_kernel<SPMV_RESID, LAY><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break; \
     default: spmm_sell_coded_kernel<SPMV_JACOBI, LAY><<<grid, block, 0, s>>>(a, kb, ldx, ldy, epi.ldb); break;        \
     }
-        if (m.sell_vbits == 4) { FAMG_SELLC(4) }
-        else if (m.sell_vbits == 8) { FAMG_SELLC(8) }
+        if (m.sell.vbits == 4) { FAMG_SELLC(4) }
+        else if (m.sell.vbits == 8) { FAMG_SELLC(8) }
         else { FAMG_SELLC(16) }
 #undef FAMG_SELLC
         FAMG_CHECK_HIP(hipGetLastError());
@@ -1171,17 +1153,17 @@ void spmm_sell_coded(const GpuCsr &m, const double *x, int64_t ldx, double *y, i
 template <int MODE>
 static void spmm_sell_t(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k,
                         const SpmmEpi &epi, hipStream_t s) {
-    if (m.nslices == 0) return;
-    const dim3 grid((unsigned)ceil_div(m.nslices, 4)), block(256);
+    if (m.sell.nslices == 0) return;
+    const dim3 grid((unsigned)ceil_div(m.sell.nslices, 4)), block(256);
     for (int64_t c0 = 0; c0 < k; c0 += SPMM_KB) {
         const int kb = (int)std::min<int64_t>(SPMM_KB, k - c0);
         Epi e{x + c0 * ldx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        SellArgs a{m.sell_row0.get(), m.sell_soff.get(), m.sell_desc.get(), m.sell_base.get(),
-                   m.sell_data.get(), 0, (int32_t)m.nslices, e, nullptr, 0, 1};
+        SellArgs a{m.sell.row0.get(), m.sell.soff.get(), m.sell.desc.get(), m.sell.base.get(),
+                   m.sell.data.get(), 0, (int32_t)m.sell.nslices, e, nullptr, 0, 1};
         double *yc = y + c0 * ldy;
         const SpmmEpiDev se{epi.b ? epi.b + c0 * epi.ldb : nullptr, epi.ldb, epi.d};
 #define FAMG_SELLMM(KB) \
-    hipLaunchKernelGGL((spmm_sell_kernel<KB, MODE>), grid, block, 0, s, a, m.sell_paired, ldx, yc, ldy, se)
+    hipLaunchKernelGGL((spmm_sell_kernel<KB, MODE>), grid, block, 0, s, a, m.sell.paired, ldx, yc, ldy, se)
         switch (kb) {
         case 1: FAMG_SELLMM(1); break;
         case 2: FAMG_SELLMM(2); break;

@@ -172,27 +172,12 @@ static bool sellp_disabled() {
     return off;
 }
 
-void sellp_release(GpuCsr &m) {
-    m.sellp_vals.release();
-    m.sellp_eoff.release();
-    m.sellp_row0.release();
-    m.sellp_pat.release();
-    m.sellp_offs.release();
-    m.sellp_rbase.release();
-    m.sellp_vtab.release();
-    m.sellp_slices = m.sellp_elems = m.sellp_ntab = m.sellp_meta_bytes = m.sellp_stream = 0;
-    m.sellp_L = 0;
-    m.sellp_vbits = 0;
-    m.sellp_seg_slc.clear();
-}
-
 // Builds the pattern-SELL storage when the rows of every slice share a small
 // set of offset patterns (a structured operator): fp64-valued operators whose
 // rows average >= 48 entries (then L >= 2 lanes per row); 4/8-bit-coded
 // operators when the pattern stream is <= 0.5 of other_bytes (the storage
 // finalize chose).  True if built.
 bool build_sellp(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes) {
-    sellp_release(m);
     if (g_spmv_format_policy != 0 || sellp_disabled() || m.no_sellp || m.nrows < 1024 || m.nnz == 0 ||
         m.ncols < 2)
         return false;
@@ -309,42 +294,42 @@ bool build_sellp(GpuCsr &m, const std::vector<int64_t> &rp, int64_t other_bytes)
             }
         }
     }
-    m.sellp_vbits = vb;
+    m.sellp.vbits = vb;
     if (vb) {
-        m.sellp_vals.resize(std::max<int64_t>(16, (int64_t)words.size() * 4));
-        FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp_vals.get(), words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
-        m.sellp_vtab.resize(tab.size());
-        FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp_vtab.get(), tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
-        m.sellp_ntab = (int64_t)tab.size();
+        m.sellp.vals.resize(std::max<int64_t>(16, (int64_t)words.size() * 4));
+        FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp.vals.get(), words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
+        m.sellp.vtab.resize(tab.size());
+        FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp.vtab.get(), tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+        m.sellp.ntab = (int64_t)tab.size();
     } else {
-        m.sellp_vals.resize(std::max<int64_t>(16, units * 8));
-        FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp_vals.get(), fv.data(), units * 8, hipMemcpyHostToDevice, st));
-        m.sellp_ntab = 0;
+        m.sellp.vals.resize(std::max<int64_t>(16, units * 8));
+        FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp.vals.get(), fv.data(), units * 8, hipMemcpyHostToDevice, st));
+        m.sellp.ntab = 0;
     }
     if (!square) {
-        m.sellp_rbase.resize(n);
-        FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp_rbase.get(), base.data(), n * 4, hipMemcpyHostToDevice, st));
+        m.sellp.rbase.resize(n);
+        FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp.rbase.get(), base.data(), n * 4, hipMemcpyHostToDevice, st));
     }
-    m.sellp_eoff.resize(ns + 1);
-    m.sellp_row0.resize(ns + 1);
+    m.sellp.eoff.resize(ns + 1);
+    m.sellp.row0.resize(ns + 1);
     std::vector<int32_t> pat(2 * std::max<int64_t>(1, ns), 0);
     for (int64_t k = 0; k < ns; k++) {
         pat[2 * k] = poff[pid[k]];
         pat[2 * k + 1] = poff[pid[k] + 1] - poff[pid[k]];
     }
-    m.sellp_pat.resize(pat.size());
-    m.sellp_offs.resize(std::max<size_t>(1, offs.size()));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp_eoff.get(), eoff.data(), (ns + 1) * 8, hipMemcpyHostToDevice, st));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp_row0.get(), row0.data(), (ns + 1) * 4, hipMemcpyHostToDevice, st));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp_pat.get(), pat.data(), pat.size() * 4, hipMemcpyHostToDevice, st));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp_offs.get(), offs.data(), offs.size() * 4, hipMemcpyHostToDevice, st));
+    m.sellp.pat.resize(pat.size());
+    m.sellp.offs.resize(std::max<size_t>(1, offs.size()));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp.eoff.get(), eoff.data(), (ns + 1) * 8, hipMemcpyHostToDevice, st));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp.row0.get(), row0.data(), (ns + 1) * 4, hipMemcpyHostToDevice, st));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp.pat.get(), pat.data(), pat.size() * 4, hipMemcpyHostToDevice, st));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.sellp.offs.get(), offs.data(), offs.size() * 4, hipMemcpyHostToDevice, st));
     FAMG_CHECK_HIP(hipStreamSynchronize(st));
-    m.sellp_slices = ns;
-    m.sellp_elems = vb ? eoff[ns] * (32 / vb) : units;
-    m.sellp_L = L;
-    m.sellp_seg_slc = seg_slc;
-    m.sellp_meta_bytes = meta;
-    m.sellp_stream = (vb ? eoff[ns] * 4 : units * 8) + meta + 8 * m.sellp_ntab;
+    m.sellp.slices = ns;
+    m.sellp.elems = vb ? eoff[ns] * (32 / vb) : units;
+    m.sellp.L = L;
+    m.sellp.seg_slc = seg_slc;
+    m.sellp.meta_bytes = meta;
+    m.sellp.stream = (vb ? eoff[ns] * 4 : units * 8) + meta + 8 * m.sellp.ntab;
     return true;
 }
 
@@ -362,11 +347,11 @@ static int sellp_spw() {
 
 void spmv_sellp(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s,
                 int64_t seg) {
-    const int64_t s0 = seg < 0 ? 0 : m.sellp_seg_slc[seg];
-    const int64_t s1 = seg < 0 ? m.sellp_slices : m.sellp_seg_slc[seg + 1];
+    const int64_t s0 = seg < 0 ? 0 : m.sellp.seg_slc[seg];
+    const int64_t s1 = seg < 0 ? m.sellp.slices : m.sellp.seg_slc[seg + 1];
     if (s1 <= s0) return;
-    SellpArgs a{m.sellp_vals.get(), m.sellp_eoff.get(), m.sellp_row0.get(),
-                reinterpret_cast<const int2 *>(m.sellp_pat.get()), m.sellp_offs.get(), m.sellp_rbase.get(), m.sellp_vtab.get(), (int32_t)m.sellp_ntab,
+    SellpArgs a{m.sellp.vals.get(), m.sellp.eoff.get(), m.sellp.row0.get(),
+                reinterpret_cast<const int2 *>(m.sellp.pat.get()), m.sellp.offs.get(), m.sellp.rbase.get(), m.sellp.vtab.get(), (int32_t)m.sellp.ntab,
                 (int32_t)s0, (int32_t)(s1 - s0), (int32_t)m.ncols, sellp_w2_enabled(), sellp_spw(), x, y, epi.b, epi.d, epi.dc, epi.dt,
                 epi.y2};
     FAMG_REQUIRE(mode != SPMV_SETDF || (epi.y2 && (epi.d || epi.dc)), AMG_ERR_INVALID, "SETDF needs y2 and d");
@@ -382,10 +367,10 @@ void spmv_sellp(const GpuCsr &m, const double *x, double *y, SpmvMode mode, cons
     default: fail(AMG_ERR_UNSUPPORTED, "pattern SELL: unsupported SpMV epilogue");                 \
     }
 #define FAMG_SELLP_VB(L)                                                                           \
-    if (m.sellp_vbits == 0) { FAMG_SELLP(L, 0) }                                                   \
-    else if (m.sellp_vbits == 4) { FAMG_SELLP(L, 4) }                                              \
+    if (m.sellp.vbits == 0) { FAMG_SELLP(L, 0) }                                                   \
+    else if (m.sellp.vbits == 4) { FAMG_SELLP(L, 4) }                                              \
     else { FAMG_SELLP(L, 8) }
-    switch (m.sellp_L) {
+    switch (m.sellp.L) {
     case 1: FAMG_SELLP_VB(1) break;
     case 2: FAMG_SELLP_VB(2) break;
     case 4: FAMG_SELLP_VB(4) break;

@@ -514,13 +514,13 @@ __global__ void k_sgs27_const(const uint32_t *codes, int cw, Sgs27Const c, int n
 // decoding each row's codes (the CST DIA kernels: the same products, the
 // cleared ones +-0.0 added to an accumulator that is never -0.0).
 bool dia_constant(GpuCsr &m) {
-    m.dia_cst = false;
-    const int K = m.dia_k;
-    if (!m.has_dia() || m.dia_rowid || m.dia_r0 != 0 || m.dia_r1 != m.nrows || (K != 27 && K != 7) ||
-        m.nrows != m.ncols || m.dia_pat)
+    m.dia.cst = false;
+    const int K = m.dia.k;
+    if (!m.dia.built() || m.dia.rowid || m.dia.r0 != 0 || m.dia.r1 != m.nrows || (K != 27 && K != 7) ||
+        m.nrows != m.ncols || m.dia.pat)
         return false;
-    if (K == 27 && !((m.dia_vbits == 4 && m.dia_cw == 4) || (m.dia_vbits == 8 && m.dia_cw == 8))) return false;
-    if (K * m.dia_vbits > 32 * m.dia_cw || m.dia_cw > 8) return false;
+    if (K == 27 && !((m.dia.vbits == 4 && m.dia.cw == 4) || (m.dia.vbits == 8 && m.dia.cw == 8))) return false;
+    if (K * m.dia.vbits > 32 * m.dia.cw || m.dia.cw > 8) return false;
     // the grid steps of diagonal k
     int st[27][3];
     for (int k = 0; k < K; k++) {
@@ -531,32 +531,32 @@ bool dia_constant(GpuCsr &m) {
             for (int q = 0; q < 3; q++) st[k][q] = s7[k][q];
         }
     }
-    const std::vector<int> &off = m.dia_off;
+    const std::vector<int> &off = m.dia.off;
     const int64_t nx = K == 27 ? off[16] : off[5], pl = K == 27 ? off[22] : off[6];
     if (nx < 2 || (nx & 1) || pl <= 0 || pl % nx != 0 || m.nrows % pl != 0) return false;
     const int64_t ny = pl / nx, nz = m.nrows / pl;
     for (int k = 0; k < K; k++)
         if (off[k] != st[k][2] * pl + st[k][1] * nx + st[k][0]) return false;
     hipStream_t s = m.ctx->stream;
-    std::vector<double> tab(m.dia_ntab);
-    FAMG_CHECK_HIP(hipMemcpyAsync(tab.data(), m.dia_vtab.get(), tab.size() * 8, hipMemcpyDeviceToHost, s));
+    std::vector<double> tab(m.dia.ntab);
+    FAMG_CHECK_HIP(hipMemcpyAsync(tab.data(), m.dia.vtab.get(), tab.size() * 8, hipMemcpyDeviceToHost, s));
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
     uint64_t bits0 = 1;
     if (!tab.empty()) std::memcpy(&bits0, &tab[0], 8);
     if (bits0 != 0) return false;  // code 0 must be +0.0
     const int64_t ic = ((nz / 2) * ny + ny / 2) * nx + nx / 2;
-    std::vector<uint32_t> w(m.dia_cw);
-    FAMG_CHECK_HIP(hipMemcpyAsync(w.data(), m.dia_codes.get() + ic * m.dia_cw, m.dia_cw * 4, hipMemcpyDeviceToHost, s));
+    std::vector<uint32_t> w(m.dia.cw);
+    FAMG_CHECK_HIP(hipMemcpyAsync(w.data(), m.dia.codes.get() + ic * m.dia.cw, m.dia.cw * 4, hipMemcpyDeviceToHost, s));
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
-    const uint32_t mask = (1u << m.dia_vbits) - 1;
+    const uint32_t mask = (1u << m.dia.vbits) - 1;
     Sgs27Const c;
-    for (int q = 0; q < 8; q++) c.icode[q] = q < m.dia_cw ? w[q] : 0xffffffffu;
+    for (int q = 0; q < 8; q++) c.icode[q] = q < m.dia.cw ? w[q] : 0xffffffffu;
     for (int f = 0; f < 6; f++)
         for (int q = 0; q < 8; q++) c.fmask[f][q] = 0;
     for (int k = 0; k < K; k++) {
         const int dx = st[k][0], dy = st[k][1], dz = st[k][2];
-        const uint32_t b = mask << ((k * m.dia_vbits) & 31);
-        const int q = (k * m.dia_vbits) >> 5;
+        const uint32_t b = mask << ((k * m.dia.vbits) & 31);
+        const int q = (k * m.dia.vbits) >> 5;
         if (dx < 0) c.fmask[0][q] |= b;
         if (dx > 0) c.fmask[1][q] |= b;
         if (dy < 0) c.fmask[2][q] |= b;
@@ -567,18 +567,18 @@ bool dia_constant(GpuCsr &m) {
     // code bits past the K diagonals must match too (they are the +0.0 padding)
     DevBuf<int> bad(1);
     FAMG_CHECK_HIP(hipMemsetAsync(bad.get(), 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_sgs27_const, dim3((unsigned)ceil_div(m.nrows, 256)), dim3(256), 0, s, m.dia_codes.get(),
-                       m.dia_cw, c, (int)nx, (int)ny, (int)nz, bad.get());
+    hipLaunchKernelGGL(k_sgs27_const, dim3((unsigned)ceil_div(m.nrows, 256)), dim3(256), 0, s, m.dia.codes.get(),
+                       m.dia.cw, c, (int)nx, (int)ny, (int)nz, bad.get());
     FAMG_CHECK_HIP(hipGetLastError());
     int hb = 1;
     FAMG_CHECK_HIP(hipMemcpyAsync(&hb, bad.get(), sizeof(int), hipMemcpyDeviceToHost, s));
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
     if (hb) return false;
-    for (int k = 0; k < K; k++) m.dia_cst_v[k] = tab[(w[(k * m.dia_vbits) >> 5] >> ((k * m.dia_vbits) & 31)) & mask];
-    m.dia_cst_n[0] = (int)nx;
-    m.dia_cst_n[1] = (int)ny;
-    m.dia_cst_n[2] = (int)nz;
-    m.dia_cst = true;
+    for (int k = 0; k < K; k++) m.dia.cst_v[k] = tab[(w[(k * m.dia.vbits) >> 5] >> ((k * m.dia.vbits) & 31)) & mask];
+    m.dia.cst_n[0] = (int)nx;
+    m.dia.cst_n[1] = (int)ny;
+    m.dia.cst_n[2] = (int)nz;
+    m.dia.cst = true;
     return true;
 }
 
@@ -590,11 +590,11 @@ void sgs27_setup(SgsOp &S) {
     S.fused27 = false;
     if (!sgs_fused_enabled() || !S.A) return;
     const GpuCsr &m = S.A->m;
-    if (m.kernel != SPMV_KERNEL_DIA || !m.has_dia() || m.dia_rowid || m.dia_r0 != 0 || m.dia_r1 != m.nrows ||
-        m.dia_k != 27 || m.nrows != m.ncols)
+    if (m.kernel != SPMV_KERNEL_DIA || !m.dia.built() || m.dia.rowid || m.dia.r0 != 0 || m.dia.r1 != m.nrows ||
+        m.dia.k != 27 || m.nrows != m.ncols)
         return;
-    if (!((m.dia_vbits == 4 && m.dia_cw == 4) || (m.dia_vbits == 8 && m.dia_cw == 8))) return;
-    const std::vector<int> &off = m.dia_off;
+    if (!((m.dia.vbits == 4 && m.dia.cw == 4) || (m.dia.vbits == 8 && m.dia.cw == 8))) return;
+    const std::vector<int> &off = m.dia.off;
     const int nx = off[16];       // diagonal (dz, dy, dx) = (0, +1, 0)
     if (nx < 2 || nx > SGS27_MAX_NX || (nx & 1)) return;  // even rows: aligned 16-B pairs
     const int64_t pl = off[22];   // diagonal (+1, 0, 0): nx * ny
@@ -610,9 +610,9 @@ void sgs27_setup(SgsOp &S) {
         if (S.host_colors[i] != (x & 1) + 2 * (y & 1) + 4 * (z & 1)) return;
     }
     // the +0.0 code: the table is sorted by bit pattern and holds +0.0
-    std::vector<double> tab(m.dia_ntab);
+    std::vector<double> tab(m.dia.ntab);
     hipStream_t s = S.ctx->stream;
-    FAMG_CHECK_HIP(hipMemcpyAsync(tab.data(), m.dia_vtab.get(), tab.size() * 8, hipMemcpyDeviceToHost, s));
+    FAMG_CHECK_HIP(hipMemcpyAsync(tab.data(), m.dia.vtab.get(), tab.size() * 8, hipMemcpyDeviceToHost, s));
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
     int zcode = -1;
     for (size_t q = 0; q < tab.size(); q++) {
@@ -623,8 +623,8 @@ void sgs27_setup(SgsOp &S) {
     if (zcode < 0) return;
     DevBuf<int> bad(1);
     FAMG_CHECK_HIP(hipMemsetAsync(bad.get(), 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_sgs27_check, dim3((unsigned)ceil_div(m.nrows, 256)), dim3(256), 0, s, m.dia_codes.get(),
-                       m.dia_cw, m.dia_vbits, zcode, nx, ny, nz, bad.get());
+    hipLaunchKernelGGL(k_sgs27_check, dim3((unsigned)ceil_div(m.nrows, 256)), dim3(256), 0, s, m.dia.codes.get(),
+                       m.dia.cw, m.dia.vbits, zcode, nx, ny, nz, bad.get());
     FAMG_CHECK_HIP(hipGetLastError());
     int hbad = 1;
     FAMG_CHECK_HIP(hipMemcpyAsync(&hbad, bad.get(), sizeof(int), hipMemcpyDeviceToHost, s));
@@ -633,22 +633,22 @@ void sgs27_setup(SgsOp &S) {
     // code group of an interior row (the grid centre) and its coefficients
     {
         const int64_t ic = ((int64_t)(nz / 2) * ny + ny / 2) * nx + nx / 2;
-        std::vector<uint32_t> w(m.dia_cw);
-        FAMG_CHECK_HIP(hipMemcpyAsync(w.data(), m.dia_codes.get() + ic * m.dia_cw, m.dia_cw * 4,
+        std::vector<uint32_t> w(m.dia.cw);
+        FAMG_CHECK_HIP(hipMemcpyAsync(w.data(), m.dia.codes.get() + ic * m.dia.cw, m.dia.cw * 4,
                                       hipMemcpyDeviceToHost, s));
         FAMG_CHECK_HIP(hipStreamSynchronize(s));
         S.icode27.assign(8, 0xffffffffu);
-        for (int q = 0; q < m.dia_cw; q++) S.icode27[q] = w[q];
+        for (int q = 0; q < m.dia.cw; q++) S.icode27[q] = w[q];
         S.icoef27.assign(27, 0.0);
-        const uint32_t mask = (1u << m.dia_vbits) - 1;
+        const uint32_t mask = (1u << m.dia.vbits) - 1;
         for (int k = 0; k < 27; k++)
-            S.icoef27[k] = tab[(w[(k * m.dia_vbits) >> 5] >> ((k * m.dia_vbits) & 31)) & mask];
+            S.icoef27[k] = tab[(w[(k * m.dia.vbits) >> 5] >> ((k * m.dia.vbits) & 31)) & mask];
         // face masks: code bits of the entries with dx = -1 / +1, dy = -1 / +1, dz = -1 / +1
         S.fmask27.assign(6 * 8, 0u);
         for (int k = 0; k < 27; k++) {
             const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
-            const uint32_t bits = mask << ((k * m.dia_vbits) & 31);
-            const int q = (k * m.dia_vbits) >> 5;
+            const uint32_t bits = mask << ((k * m.dia.vbits) & 31);
+            const int q = (k * m.dia.vbits) >> 5;
             if (dx < 0) S.fmask27[0 * 8 + q] |= bits;
             if (dx > 0) S.fmask27[1 * 8 + q] |= bits;
             if (dy < 0) S.fmask27[2 * 8 + q] |= bits;
@@ -667,7 +667,7 @@ void sgs27_setup(SgsOp &S) {
             for (int q = 0; q < 8; q++) c.fmask[f][q] = S.fmask27[f * 8 + q];
         FAMG_CHECK_HIP(hipMemsetAsync(bad.get(), 0, sizeof(int), s));
         hipLaunchKernelGGL(k_sgs27_const, dim3((unsigned)ceil_div(m.nrows, 256)), dim3(256), 0, s,
-                           m.dia_codes.get(), m.dia_cw, c, nx, ny, nz, bad.get());
+                           m.dia.codes.get(), m.dia.cw, c, nx, ny, nz, bad.get());
         FAMG_CHECK_HIP(hipGetLastError());
         int hb = 1;
         FAMG_CHECK_HIP(hipMemcpyAsync(&hb, bad.get(), sizeof(int), hipMemcpyDeviceToHost, s));
@@ -692,9 +692,9 @@ static void sgs27_phase(const SgsOp &S, int pz, int nst, const int *px, const in
     const int nplanes = (S.nz27 - pz + 1) / 2;
     if (nplanes <= 0) return;
     Sgs27Args a{};
-    a.codes = m.dia_codes.get();
-    a.vtab = m.dia_vtab.get();
-    a.ntab = (int)m.dia_ntab;
+    a.codes = m.dia.codes.get();
+    a.vtab = m.dia.vtab.get();
+    a.ntab = (int)m.dia.ntab;
     a.nx = S.nx27;
     a.ny = S.ny27;
     a.nz = S.nz27;
@@ -726,7 +726,7 @@ static void sgs27_phase(const SgsOp &S, int pz, int nst, const int *px, const in
     // and b, the other parity's x read once (unless zero), the copied planes
     if (g_launch_log)
         log_launch("sgs27_phase", SPMV_KERNEL_DIA, SPMV_SGS, rows,
-                   rows * (8 + (S.const27 ? 0 : 4 * (int64_t)m.dia_cw) + 8) + (own_zero ? 0 : rows * 8) +
+                   rows * (8 + (S.const27 ? 0 : 4 * (int64_t)m.dia.cw) + 8) + (own_zero ? 0 : rows * 8) +
                        (other_zero ? 0 : (int64_t)(m.nrows - rows) * 8) +
                        (cpy_src ? (int64_t)(m.nrows - rows) * 16 : 0));
     constexpr int MPFS = 3, MPFO = 4;  // march: pairs per thread of a tile's own rows / a plane's rows
@@ -773,14 +773,14 @@ static void sgs27_phase(const SgsOp &S, int pz, int nst, const int *px, const in
     if (S.const27) k_sgs27_phase<VB, CW, U, NW, true, false><<<grid, dim3(64 * NW), lds, s>>>(a);   \
     else k_sgs27_phase<VB, CW, U, NW, false, false><<<grid, dim3(64 * NW), lds, s>>>(a)
     if (ol) {
-        if (m.dia_vbits == 4) {
+        if (m.dia.vbits == 4) {
             if (S.const27) k_sgs27_phase<4, 4, 1, 16, true, true><<<grid, dim3(1024), lds, s>>>(a);
             else k_sgs27_phase<4, 4, 1, 16, false, true><<<grid, dim3(1024), lds, s>>>(a);
         } else {
             if (S.const27) k_sgs27_phase<8, 8, 1, 16, true, true><<<grid, dim3(1024), lds, s>>>(a);
             else k_sgs27_phase<8, 8, 1, 16, false, true><<<grid, dim3(1024), lds, s>>>(a);
         }
-    } else if (m.dia_vbits == 4) {
+    } else if (m.dia.vbits == 4) {
         if (nw == 8) { if (u2) FAMG_SGS27_LAUNCH(4, 4, 2, 8); else FAMG_SGS27_LAUNCH(4, 4, 1, 8); }
         else { if (u2) FAMG_SGS27_LAUNCH(4, 4, 2, 4); else FAMG_SGS27_LAUNCH(4, 4, 1, 4); }
     } else {

@@ -301,15 +301,15 @@ __global__ __launch_bounds__(256) void spmm_sellp_kernel(SpmmSellpArgs a) {
 // e: its operands B (advanced with the column group here), ldb, d.
 enum SpmmKind { SPMM_NONE, SPMM_DIA, SPMM_SCS, SPMM_BSR, SPMM_SELLP, SPMM_XS };
 static SpmmKind spmm_kind(const GpuCsr &m) {
-    const int sL = m.sellp_L, sV = m.sellp_vbits;
-    if (m.kernel == SPMV_KERNEL_XS && m.has_xs()) return SPMM_XS;
-    if (m.kernel == SPMV_KERNEL_DIA && m.has_dia() && !m.dia_rowid && m.dia_r0 == 0 && m.dia_r1 == m.nrows &&
-        m.dia_k <= 64)
+    const int sL = m.sellp.L, sV = m.sellp.vbits;
+    if (m.kernel == SPMV_KERNEL_XS && m.xs.built()) return SPMM_XS;
+    if (m.kernel == SPMV_KERNEL_DIA && m.dia.built() && !m.dia.rowid && m.dia.r0 == 0 && m.dia.r1 == m.nrows &&
+        m.dia.k <= 64)
         return SPMM_DIA;
     // (eight lanes per row: no k-wide kernel sums in that order, spmm_epi runs one SpMV per column)
-    if (m.kernel == SPMV_KERNEL_SCS && m.has_scs() && m.scs_seg < 0 && xscs_row_lanes(m) == 1) return SPMM_SCS;
-    if (m.kernel == SPMV_KERNEL_BSR && m.has_bsr()) return SPMM_BSR;
-    if (m.kernel == SPMV_KERNEL_SELLP && m.has_sellp() && m.sellp_seg_slc.size() <= 2 &&
+    if (m.kernel == SPMV_KERNEL_SCS && m.scs.built() && m.scs.seg < 0 && xscs_row_lanes(m) == 1) return SPMM_SCS;
+    if (m.kernel == SPMV_KERNEL_BSR && m.bsr.built()) return SPMM_BSR;
+    if (m.kernel == SPMV_KERNEL_SELLP && m.sellp.built() && m.sellp.seg_slc.size() <= 2 &&
         (sL == 1 || sL == 2 || sL == 4 || sL == 8 || sL == 16 || sL == 32 || sL == 64) &&
         (sV == 0 || sV == 4 || sV == 8))
         return SPMM_SELLP;
@@ -317,7 +317,7 @@ static SpmmKind spmm_kind(const GpuCsr &m) {
 }
 
 bool spmm_has_kernel(const GpuCsr &m) {
-    return spmm_kind(m) != SPMM_NONE || (m.kernel == SPMV_KERNEL_SELL && !m.sell_vbits);
+    return spmm_kind(m) != SPMM_NONE || (m.kernel == SPMV_KERNEL_SELL && !m.sell.vbits);
 }
 
 template <int MODE>
@@ -326,7 +326,7 @@ static bool spmm_compressed_t(const GpuCsr &m, const double *x, int64_t ldx, dou
     const SpmmKind kind = spmm_kind(m);
     const bool dia = kind == SPMM_DIA, scs = kind == SPMM_SCS, bsr = kind == SPMM_BSR, xs = kind == SPMM_XS;
     const bool sellp = kind == SPMM_SELLP;
-    const int sL = m.sellp_L, sV = m.sellp_vbits;
+    const int sL = m.sellp.L, sV = m.sellp.vbits;
     if (xs) {  // xsell.hip: per column with its x chunks in LDS
         if constexpr (MODE == SPMV_SET) return spmm_xs(m, x, ldx, y, ldy, k, s);
         else return spmm_xs_epi(m, x, ldx, y, ldy, k, (SpmvMode)MODE, SpmmEpi{e0.b, e0.ldb, e0.d}, s);
@@ -340,20 +340,20 @@ static bool spmm_compressed_t(const GpuCsr &m, const double *x, int64_t ldx, dou
         const SpmmEpiDev e{e0.b ? e0.b + c0 * e0.ldb : nullptr, e0.ldb, e0.d};
         if (dia) {
             SpmmDiaArgs a{};
-            a.codes = m.dia_codes.get();
-            a.vtab = m.dia_vtab.get();
-            a.ntab = (int32_t)m.dia_ntab;
-            a.k = m.dia_k;
+            a.codes = m.dia.codes.get();
+            a.vtab = m.dia.vtab.get();
+            a.ntab = (int32_t)m.dia.ntab;
+            a.k = m.dia.k;
             a.nrows = (int32_t)m.nrows;
             a.ncols = (int32_t)m.ncols;
-            for (int q = 0; q < m.dia_k; q++) a.off[q] = m.dia_off[q];
+            for (int q = 0; q < m.dia.k; q++) a.off[q] = m.dia.off[q];
             a.x = xc;
             a.ldx = ldx;
             a.y = yc;
             a.ldy = ldy;
             a.e = e;
             const dim3 grid((unsigned)ceil_div(m.nrows, 256)), block(256);
-            const int key = m.dia_vbits * 16 + m.dia_cw;
+            const int key = m.dia.vbits * 16 + m.dia.cw;
 #define FAMG_L41(KB) spmm_dia_kernel<4, 1, KB, MODE><<<grid, block, 0, s>>>(a)
 #define FAMG_L42(KB) spmm_dia_kernel<4, 2, KB, MODE><<<grid, block, 0, s>>>(a)
 #define FAMG_L44(KB) spmm_dia_kernel<4, 4, KB, MODE><<<grid, block, 0, s>>>(a)
@@ -376,26 +376,26 @@ static bool spmm_compressed_t(const GpuCsr &m, const double *x, int64_t ldx, dou
             default: fail(AMG_ERR_INVALID, "SpMM: unsupported DIA code layout");
             }
         } else if (scs) {
-            SpmmScsArgs a{m.scs_cls.get(), m.scs_dict.get(), m.scs_offs.get(), (int32_t)m.scs_k,
+            SpmmScsArgs a{m.scs.cls.get(), m.scs.dict.get(), m.scs.offs.get(), (int32_t)m.scs.k,
                           (int32_t)m.nrows, (int32_t)m.ncols, xc, ldx, yc, ldy, e};
-            const dim3 grid((unsigned)ceil_div(m.nrows, m.scs_lanes ? 4 : 256)), block(256);
+            const dim3 grid((unsigned)ceil_div(m.nrows, m.scs.lanes ? 4 : 256)), block(256);
 #define FAMG_S1(KB) spmm_scs_kernel<1, KB, MODE><<<grid, block, 0, s>>>(a)
 #define FAMG_S2(KB) spmm_scs_kernel<2, KB, MODE><<<grid, block, 0, s>>>(a)
 #define FAMG_SL1(KB) spmm_scs_lanes_kernel<1, KB, MODE><<<grid, block, 0, s>>>(a)
 #define FAMG_SL2(KB) spmm_scs_lanes_kernel<2, KB, MODE><<<grid, block, 0, s>>>(a)
-            if (m.scs_lanes) {
-                if (m.scs_ib == 1) { FAMG_SPMM_KB(kb, FAMG_SL1) }
+            if (m.scs.lanes) {
+                if (m.scs.ib == 1) { FAMG_SPMM_KB(kb, FAMG_SL1) }
                 else { FAMG_SPMM_KB(kb, FAMG_SL2) }
             } else {
-                if (m.scs_ib == 1) { FAMG_SPMM_KB(kb, FAMG_S1) }
+                if (m.scs.ib == 1) { FAMG_SPMM_KB(kb, FAMG_S1) }
                 else { FAMG_SPMM_KB(kb, FAMG_S2) }
             }
         } else if (sellp) {
-            SpmmSellpArgs a{m.sellp_vals.get(), m.sellp_eoff.get(), m.sellp_row0.get(),
-                            reinterpret_cast<const int2 *>(m.sellp_pat.get()), m.sellp_offs.get(), m.sellp_rbase.get(),
-                            m.sellp_vtab.get(), (int32_t)m.sellp_ntab, (int32_t)m.sellp_slices, (int32_t)m.ncols,
+            SpmmSellpArgs a{m.sellp.vals.get(), m.sellp.eoff.get(), m.sellp.row0.get(),
+                            reinterpret_cast<const int2 *>(m.sellp.pat.get()), m.sellp.offs.get(), m.sellp.rbase.get(),
+                            m.sellp.vtab.get(), (int32_t)m.sellp.ntab, (int32_t)m.sellp.slices, (int32_t)m.ncols,
                             xc, ldx, yc, ldy, e};
-            const dim3 grid((unsigned)ceil_div(m.sellp_slices, 4)), block(256);
+            const dim3 grid((unsigned)ceil_div(m.sellp.slices, 4)), block(256);
 #define FAMG_P(L, VB, KB) spmm_sellp_kernel<L, VB, KB, MODE><<<grid, block, 0, s>>>(a)
 #define FAMG_PL(L, VB)                                                                              \
     {                                                                                               \
@@ -426,9 +426,9 @@ static bool spmm_compressed_t(const GpuCsr &m, const double *x, int64_t ldx, dou
 #undef FAMG_PL
 #undef FAMG_P
         } else {
-            SpmmBsrArgs a{m.bsr_data.get(), m.bsr_row0.get(), m.bsr_soff.get(), (int32_t)m.bsr_slices,
+            SpmmBsrArgs a{m.bsr.data.get(), m.bsr.row0.get(), m.bsr.soff.get(), (int32_t)m.bsr.slices,
                           xc, ldx, yc, ldy, e};
-            const dim3 grid((unsigned)ceil_div(m.bsr_slices, 4)), block(256);
+            const dim3 grid((unsigned)ceil_div(m.bsr.slices, 4)), block(256);
 #define FAMG_B(KB) spmm_bsr3_kernel<KB, MODE><<<grid, block, 0, s>>>(a)
             FAMG_SPMM_KB(kb, FAMG_B)
         }

@@ -436,10 +436,6 @@ __global__ __launch_bounds__(256) void k_vec_fill(const int64_t *rp, const int32
 }
 
 static void build_vec_codes(GpuCsr &m) {
-    m.vec_codes.release();
-    m.vec_off.release();
-    m.vec_vbits = 0;
-    m.vec_o16 = false;
     if (m.nnz == 0) return;
     hipStream_t s = m.ctx->stream;
     std::vector<unsigned long long> tab;
@@ -455,20 +451,20 @@ static void build_vec_codes(GpuCsr &m) {
     const bool o16 = g_value_codes && hmx <= 32767;
     if (!vb && !o16) return;
     if (vb) {
-        m.sell_vtab.resize(tab.size());
-        FAMG_CHECK_HIP(hipMemcpyAsync(m.sell_vtab.get(), tab.data(), tab.size() * sizeof(double),
+        m.vec.vtab.resize(tab.size());
+        FAMG_CHECK_HIP(hipMemcpyAsync(m.vec.vtab.get(), tab.data(), tab.size() * sizeof(double),
                                       hipMemcpyHostToDevice, s));
-        m.vec_codes.resize(m.nnz * (vb / 8));
+        m.vec.codes.resize(m.nnz * (vb / 8));
     }
-    if (o16) m.vec_off.resize(m.nnz);
+    if (o16) m.vec.off.resize(m.nnz);
     hipLaunchKernelGGL(k_vec_fill, dim3((unsigned)ceil_div(m.nrows, 256)), dim3(256), 0, s, m.rp64.get(), m.col.get(),
-                       m.val.get(), m.nrows, vb, reinterpret_cast<const unsigned long long *>(m.sell_vtab.get()),
-                       (int)tab.size(), o16, (void *)m.vec_codes.get(), m.vec_off.get());
+                       m.val.get(), m.nrows, vb, reinterpret_cast<const unsigned long long *>(m.vec.vtab.get()),
+                       (int)tab.size(), o16, (void *)m.vec.codes.get(), m.vec.off.get());
     FAMG_CHECK_HIP(hipGetLastError());
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
-    m.vec_vbits = vb;
-    m.vec_o16 = o16;
-    m.sell_ntab = vb ? (int64_t)tab.size() : 0;
+    m.vec.vbits = vb;
+    m.vec.o16 = o16;
+    m.vec.ntab = vb ? (int64_t)tab.size() : 0;
 }
 
 // waves per row of the wave-per-row kernel: few long rows get 2 or 4 waves each.
@@ -483,22 +479,22 @@ static int vec_waves_per_row(int64_t rows, int64_t nnz) {
 }
 
 void choose_kernel(GpuCsr &m) {
-    if (m.has_dia() && !m.dia_rowid && m.dia_r0 == 0 && m.dia_r1 == m.nrows) m.kernel = SPMV_KERNEL_DIA;
-    else if (m.has_bsr()) m.kernel = SPMV_KERNEL_BSR;
+    if (m.dia.built() && !m.dia.rowid && m.dia.r0 == 0 && m.dia.r1 == m.nrows) m.kernel = SPMV_KERNEL_DIA;
+    else if (m.bsr.built()) m.kernel = SPMV_KERNEL_BSR;
     else if (m.kind_pin == 1) {  // a renumbered copy of a wave-per-row matrix (reorder.hip)
         m.kernel = SPMV_KERNEL_VECTOR;
-        m.vec_wpr = vec_waves_per_row(m.nrows, m.nnz);
+        m.vec.wpr = vec_waves_per_row(m.nrows, m.nnz);
         build_vec_codes(m);
     }
     else if (m.kind_pin == 2) m.kernel = SPMV_KERNEL_STREAM;
-    else if (m.has_scs() && m.scs_seg < 0) m.kernel = SPMV_KERNEL_SCS;
-    else if (m.has_sellp()) m.kernel = SPMV_KERNEL_SELLP;
-    else if (m.has_xs()) m.kernel = SPMV_KERNEL_XS;
-    else if (m.has_sell()) m.kernel = SPMV_KERNEL_SELL;
+    else if (m.scs.built() && m.scs.seg < 0) m.kernel = SPMV_KERNEL_SCS;
+    else if (m.sellp.built()) m.kernel = SPMV_KERNEL_SELLP;
+    else if (m.xs.built()) m.kernel = SPMV_KERNEL_XS;
+    else if (m.sell.built()) m.kernel = SPMV_KERNEL_SELL;
     else if (g_spmv_format_policy == 3 ||
              (g_spmv_format_policy == 0 && m.nrows > 0 && m.nnz >= vec_min_avg() * m.nrows)) {
         m.kernel = SPMV_KERNEL_VECTOR;
-        m.vec_wpr = vec_waves_per_row(m.nrows, m.nnz);
+        m.vec.wpr = vec_waves_per_row(m.nrows, m.nnz);
         build_vec_codes(m);
     }
     else m.kernel = SPMV_KERNEL_STREAM;
@@ -521,12 +517,12 @@ SpmvRoute spmv_route(const GpuCsr &m, SpmvMode mode, const SpmvEpi &epi, int64_t
         r.name = name;
     };
     const bool overlay = seg < 0 || m.rframe.on();
-    if (m.gtx_on && overlay && gtx_supports(m, mode)) {
+    if (m.gtx.built() && overlay && gtx_supports(m, mode)) {
         to(ROUTE_GTX, SPMV_KERNEL_GTC, "gtx");
         r.dk = (mode == SPMV_ADD0 || mode == SPMV_SETDF) && epi_dconst(epi);
         return r;
     }
-    if (m.gtc_on && overlay && gtc_supports(m, mode)) {
+    if (m.gtc.built() && overlay && gtc_supports(m, mode)) {
         to(ROUTE_GTC, SPMV_KERNEL_GTC, "gtc");
         r.dk = (mode == SPMV_ADD0 || mode == SPMV_SETDF) && epi_dconst(epi);
         return r;
@@ -536,21 +532,21 @@ SpmvRoute spmv_route(const GpuCsr &m, SpmvMode mode, const SpmvEpi &epi, int64_t
     if (m.kernel == SPMV_KERNEL_BSR) {
         FAMG_REQUIRE(mode != SPMV_SGS, AMG_ERR_UNSUPPORTED, "block storage has no SGS sweep");
         to(ROUTE_BSR, SPMV_KERNEL_BSR, "bsr3");
-    } else if (m.kernel == SPMV_KERNEL_SCS || (m.has_scs() && seg >= 0 && seg == m.scs_seg && mode != SPMV_SGS)) {
+    } else if (m.kernel == SPMV_KERNEL_SCS || (m.scs.built() && seg >= 0 && seg == m.scs.seg && mode != SPMV_SGS)) {
         FAMG_REQUIRE(mode != SPMV_SGS, AMG_ERR_UNSUPPORTED, "stencil-class storage has no SGS sweep");
         const bool xscs = scs_takes_xscs(m, seg);
-        to(ROUTE_SCS, SPMV_KERNEL_SCS, xscs ? "xscs" : m.scs_lanes ? "scs_lanes" : "scs");
+        to(ROUTE_SCS, SPMV_KERNEL_SCS, xscs ? "xscs" : m.scs.lanes ? "scs_lanes" : "scs");
         r.rc = xscs && epi.dc;
     } else if (m.kernel == SPMV_KERNEL_XS && seg < 0 && xs_supports(mode)) {  // other modes: CSR-stream below
         to(ROUTE_XS, SPMV_KERNEL_XS, "xsell");
     } else if (m.kernel == SPMV_KERNEL_SELLP) {
         FAMG_REQUIRE(mode != SPMV_SGS, AMG_ERR_UNSUPPORTED, "pattern SELL has no SGS sweep");
         to(ROUTE_SELLP, SPMV_KERNEL_SELLP, "sellp");
-    } else if (mode == SPMV_SGS && m.has_dia() && m.dia_rowid) {  // color sweep of a color-permuted copy
+    } else if (mode == SPMV_SGS && m.dia.built() && m.dia.rowid) {  // color sweep of a color-permuted copy
         r.to = ROUTE_DIA_SGS;
         dia_route(m, epi, r);
     } else if (m.kernel == SPMV_KERNEL_DIA ||
-               (m.has_dia() && !m.dia_rowid && seg >= 0 && seg == m.dia_seg && mode != SPMV_SGS)) {
+               (m.dia.built() && !m.dia.rowid && seg >= 0 && seg == m.dia.seg && mode != SPMV_SGS)) {
         FAMG_REQUIRE(mode != SPMV_SGS, AMG_ERR_UNSUPPORTED, "DIA storage has no SGS sweep");
         r.to = ROUTE_DIA;
         dia_route(m, epi, r);
@@ -576,12 +572,12 @@ static void log_spmv(const GpuCsr &m, SpmvMode mode, const SpmvEpi &epi, const S
     const int64_t csr_mat = part(m.index_bytes());
     int64_t mat = 0;
     switch (rt.to) {
-    case ROUTE_GTX: mat = 2 * part(m.nrows) + 12 * m.gtx_nent + 8 * m.gtx_nclass; break;
-    case ROUTE_GTC: mat = part(m.nrows) + 2 * (int64_t)m.gtc_nce + 8 * (int64_t)m.gtc_ntab; break;
-    case ROUTE_SCS: mat = m.scs_ib * r + 8 * m.scs_k * m.scs_nclass + 4 * m.scs_k; break;
+    case ROUTE_GTX: mat = m.gtx.stream_bytes(part(m.nrows)); break;
+    case ROUTE_GTC: mat = m.gtc.stream_bytes(part(m.nrows)); break;
+    case ROUTE_SCS: mat = m.scs.stream_bytes(r); break;
     case ROUTE_XS: mat = m.stream_bytes(); break;
-    case ROUTE_DIA_SGS: mat = 4 * (int64_t)m.dia_cw * r + 8 * m.dia_ntab; break;
-    case ROUTE_DIA: mat = rt.cst ? (int64_t)m.dia_k * 8 : 4 * (int64_t)m.dia_cw * r + 8 * m.dia_ntab; break;
+    case ROUTE_DIA_SGS: mat = 4 * (int64_t)m.dia.cw * r + 8 * m.dia.ntab; break;
+    case ROUTE_DIA: mat = rt.cst ? (int64_t)m.dia.k * 8 : 4 * (int64_t)m.dia.cw * r + 8 * m.dia.ntab; break;
     case ROUTE_STREAM: mat = csr_mat; break;
     default: mat = part(m.stream_bytes()); break;  // BSR, SELLP, SELL, VECTOR: the finalized storage
     }
@@ -606,11 +602,11 @@ static void log_spmv(const GpuCsr &m, SpmvMode mode, const SpmvEpi &epi, const S
 #define FAMG_VEC(VB, O16, W) , VB, O16, W
 static void spmv_vector(const GpuCsr &m, const Epi &e, SpmvMode mode, hipStream_t s, const SpmvRoute &r) {
     if (r.r1 <= r.r0) return;
-    VecArgs a{m.rp32.get(), m.col.get(), m.vec_off.get(), m.val.get(), m.vec_codes.get(), m.sell_vtab.get(),
+    VecArgs a{m.rp32.get(), m.col.get(), m.vec.off.get(), m.val.get(), m.vec.codes.get(), m.vec.vtab.get(),
               (int32_t)r.r0, (int32_t)(r.r1 - r.r0), e};
-    const int wpr = flag(FLAG_VEC_WPR) ? (int)flag(FLAG_VEC_WPR) : m.vec_wpr;
+    const int wpr = flag(FLAG_VEC_WPR) ? (int)flag(FLAG_VEC_WPR) : m.vec.wpr;
     const dim3 grid((unsigned)ceil_div(r.r1 - r.r0, 4 / wpr)), block(256);
-    const int key = m.vec_vbits * 2 + (m.vec_o16 ? 1 : 0);
+    const int key = m.vec.vbits * 2 + (m.vec.o16 ? 1 : 0);
 #define FAMG_VECW(W)                                                                                   \
     switch (key) {                                                                                 \
     case 0: FAMG_LAUNCH_MODES(spmv_vector_kernel, grid, block, s, a, FAMG_VEC(0, false, W)) break;  \
@@ -662,7 +658,7 @@ void spmv(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const Spmv
 
 void spmm(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k, hipStream_t s) {
     if (spmm_compressed(m, x, ldx, y, ldy, k, s)) return;  // DIA codes, stencil classes, 3x3 blocks (spmm.hip)
-    if (m.kernel == SPMV_KERNEL_SELL && !m.sell_vbits) {
+    if (m.kernel == SPMV_KERNEL_SELL && !m.sell.vbits) {
         spmm_sell(m, x, ldx, y, ldy, k, s);
         return;
     }
@@ -696,8 +692,8 @@ static void log_spmm(const GpuCsr &m, SpmvMode mode, int64_t k, bool gtc = false
     static const char *const names[] = {"spmm_stream", "spmm_sell", "spmm_vector", "spmm_dia", "spmm_bsr3",
                                         "spmm_sellp",  "spmm_scs",  "spmm_xsell"};
     const int64_t r = m.nrows;
-    const int64_t mat = gtc ? r + 2 * (int64_t)m.gtc_nce + 8 * (int64_t)m.gtc_ntab
-                        : m.kernel == SPMV_KERNEL_DIA ? 4 * (int64_t)m.dia_cw * r + 8 * m.dia_ntab : m.stream_bytes();
+    const int64_t mat = gtc ? r + 2 * (int64_t)m.gtc.nce + 8 * (int64_t)m.gtc.ntab
+                        : m.kernel == SPMV_KERNEL_DIA ? 4 * (int64_t)m.dia.cw * r + 8 * m.dia.ntab : m.stream_bytes();
     int64_t vec = 8 * m.ncols;
     switch (mode) {
     case SPMV_SET: vec += 8 * r; break;
@@ -725,8 +721,8 @@ void spmm_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t 
     // single-vector call makes: the grid-transfer overlays first (gtx per column, gtc
     // k-wide; they sum a row in one lane, the storage below them need not), then the
     // SpMM kernels, then value-coded SELL-64 and CSR-stream.
-    const bool gtx_first = m.gtx_on && gtx_supports(m, mode);
-    const bool gtc_first = !gtx_first && m.gtc_on && gtc_supports(m, mode);
+    const bool gtx_first = m.gtx.built() && gtx_supports(m, mode);
+    const bool gtc_first = !gtx_first && m.gtc.built() && gtc_supports(m, mode);
     if (gtc_first && !m.rframe.on()) {
         if (g_launch_log) log_spmm(m, mode, k, true);
         spmm_gtc(m, x, ldx, y, ldy, k, mode, s);
@@ -739,7 +735,7 @@ void spmm_epi(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t 
         else if (!spmm_compressed_epi(m, x, ldx, y, ldy, k, mode, epi, s)) spmm_sell_epi(m, x, ldx, y, ldy, k, mode, epi, s);
         return;
     }
-    if (!overlay && m.kernel == SPMV_KERNEL_SELL && m.sell_vbits) {
+    if (!overlay && m.kernel == SPMV_KERNEL_SELL && m.sell.vbits) {
         if (g_launch_log) log_spmm(m, mode, k);
         spmm_sell_coded(m, x, ldx, y, ldy, k, mode, epi, s);
         return;

@@ -198,23 +198,23 @@ __global__ __launch_bounds__(XS_BS) void spmm_xs_group_kernel(XsArgs a, int kb, 
 template <int MODE>
 static bool spmm_xs_t(const GpuCsr &m, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t k,
                       const SpmmEpi &epi, hipStream_t s) {
-    if (m.kernel != SPMV_KERNEL_XS || !m.has_xs()) return false;
+    if (m.kernel != SPMV_KERNEL_XS || !m.xs.built()) return false;
     if (m.nrows == 0 || k == 0) return true;
     XsArgs a{};
-    a.data = m.xs_data.get();
-    a.desc = m.xs_desc.get();
-    a.soff = m.xs_soff.get();
-    a.coff = m.xs_coff.get();
-    a.chunks = m.xs_chunks.get();
+    a.data = m.xs.data.get();
+    a.desc = m.xs.desc.get();
+    a.soff = m.xs.soff.get();
+    a.coff = m.xs.coff.get();
+    a.chunks = m.xs.chunks.get();
     a.nrows = (int32_t)m.nrows;
     a.ncols = (int32_t)m.ncols;
-    a.ngroups = (int32_t)m.xs_groups;
+    a.ngroups = (int32_t)m.xs.groups;
     a.d = epi.d;
     for (int64_t c0 = 0; c0 < k; c0 += 8) {
         a.x = x + c0 * ldx;
         a.y = y + c0 * ldy;
         a.b = epi.b ? epi.b + c0 * epi.ldb : nullptr;
-        spmm_xs_group_kernel<MODE><<<dim3((unsigned)m.xs_groups), dim3(XS_BS), 0, s>>>(
+        spmm_xs_group_kernel<MODE><<<dim3((unsigned)m.xs.groups), dim3(XS_BS), 0, s>>>(
             a, (int)std::min<int64_t>(8, k - c0), ldx, ldy, epi.ldb);
         FAMG_CHECK_HIP(hipGetLastError());
     }
@@ -579,15 +579,6 @@ static bool xs_disabled() {
     return off;
 }
 
-void xs_release(GpuCsr &m) {
-    m.xs_data.release();
-    m.xs_desc.release();
-    m.xs_soff.release();
-    m.xs_coff.release();
-    m.xs_chunks.release();
-    m.xs_groups = m.xs_bytes = m.xs_steps = m.xs_chunk_total = m.xs_escape_slices = m.xs_maxw = 0;
-}
-
 // Built for a single-segment matrix of >= XS_MIN_GROUPS groups (one workgroup
 // per group: fewer leave CUs idle -- P_2 of the 256^3 cycle, 64 groups, ran 45 us
 // against 21 us on SELL-64) whose SELL copy gathers (fewer than half of its
@@ -596,9 +587,8 @@ void xs_release(GpuCsr &m) {
 constexpr int64_t XS_MIN_GROUPS = 512;
 
 bool build_xs(GpuCsr &m, const std::vector<int64_t> &rp) {
-    xs_release(m);
-    if (xs_disabled() || g_spmv_format_policy != 0 || m.no_sellp || m.seg_rows.size() != 2 || !m.has_sell() ||
-        m.sell_vbits != 0 || m.nrows < (XS_MIN_GROUPS - 1) * XS_ROWS + 1 || 2 * m.sell_mode_slices[0] >= m.nslices ||
+    if (xs_disabled() || g_spmv_format_policy != 0 || m.no_sellp || m.seg_rows.size() != 2 || !m.sell.built() ||
+        m.sell.vbits != 0 || m.nrows < (XS_MIN_GROUPS - 1) * XS_ROWS + 1 || 2 * m.sell.mode_slices[0] >= m.sell.nslices ||
         m.ncols >= (1 << 30))
         return false;
     const int64_t n = m.nrows, ns = (n + 63) / 64, ng = (ns + XS_SLICES - 1) / XS_SLICES;
@@ -663,26 +653,26 @@ bool build_xs(GpuCsr &m, const std::vector<int64_t> &rp) {
         chunks.insert(chunks.end(), gch[g].begin(), gch[g].end());
         coff[g + 1] = (int32_t)chunks.size();
     }
-    m.xs_data.resize(std::max<int64_t>(128, bytes));  // every slice has >= 1 step: no load leaves it
-    m.xs_desc.resize(ns);
-    m.xs_soff.resize(ns + 1);
-    m.xs_coff.resize(ng + 1);
-    m.xs_chunks.resize(chunks.size());
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.xs_desc.get(), desc.data(), ns * 4, hipMemcpyHostToDevice, st));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.xs_soff.get(), soff.data(), (ns + 1) * 4, hipMemcpyHostToDevice, st));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.xs_coff.get(), coff.data(), (ng + 1) * 4, hipMemcpyHostToDevice, st));
-    FAMG_CHECK_HIP(hipMemcpyAsync(m.xs_chunks.get(), chunks.data(), chunks.size() * 4, hipMemcpyHostToDevice, st));
+    m.xs.data.resize(std::max<int64_t>(128, bytes));  // every slice has >= 1 step: no load leaves it
+    m.xs.desc.resize(ns);
+    m.xs.soff.resize(ns + 1);
+    m.xs.coff.resize(ng + 1);
+    m.xs.chunks.resize(chunks.size());
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.xs.desc.get(), desc.data(), ns * 4, hipMemcpyHostToDevice, st));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.xs.soff.get(), soff.data(), (ns + 1) * 4, hipMemcpyHostToDevice, st));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.xs.coff.get(), coff.data(), (ng + 1) * 4, hipMemcpyHostToDevice, st));
+    FAMG_CHECK_HIP(hipMemcpyAsync(m.xs.chunks.get(), chunks.data(), chunks.size() * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_xs_fill, dim3((unsigned)ceil_div(ns * 64, 256)), dim3(256), 0, st, m.rp64.get(), m.col.get(),
-                       m.val.get(), n, ns, m.xs_desc.get(), m.xs_soff.get(), m.xs_coff.get(), m.xs_chunks.get(),
-                       m.xs_data.get());
+                       m.val.get(), n, ns, m.xs.desc.get(), m.xs.soff.get(), m.xs.coff.get(), m.xs.chunks.get(),
+                       m.xs.data.get());
     FAMG_CHECK_HIP(hipGetLastError());
     FAMG_CHECK_HIP(hipStreamSynchronize(st));
-    m.xs_groups = ng;
-    m.xs_bytes = bytes;
-    m.xs_steps = soff[ns];
-    m.xs_chunk_total = (int64_t)chunks.size();
-    m.xs_escape_slices = esc;
-    m.xs_maxw = *std::max_element(w.begin(), w.end());
+    m.xs.groups = ng;
+    m.xs.bytes = bytes;
+    m.xs.steps = soff[ns];
+    m.xs.chunk_total = (int64_t)chunks.size();
+    m.xs.escape_slices = esc;
+    m.xs.maxw = *std::max_element(w.begin(), w.end());
     return true;
 }
 
@@ -690,9 +680,9 @@ bool xs_supports(SpmvMode mode) { return mode != SPMV_SGS; }
 
 #define FAMG_COMMA ,
 void spmv_xs(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const SpmvEpi &epi, hipStream_t s) {
-    XsArgs a{m.xs_data.get(), m.xs_desc.get(), m.xs_soff.get(), m.xs_coff.get(), m.xs_chunks.get(),
-             (int32_t)m.nrows, (int32_t)m.ncols, (int32_t)m.xs_groups, x, y, epi.b, epi.d, epi.dc, epi.dt};
-    const dim3 grid((unsigned)m.xs_groups), block(XS_BS);
+    XsArgs a{m.xs.data.get(), m.xs.desc.get(), m.xs.soff.get(), m.xs.coff.get(), m.xs.chunks.get(),
+             (int32_t)m.nrows, (int32_t)m.ncols, (int32_t)m.xs.groups, x, y, epi.b, epi.d, epi.dc, epi.dt};
+    const dim3 grid((unsigned)m.xs.groups), block(XS_BS);
 // T: the template arguments after the mode (empty, or ", NB")
 #define FAMG_XS_LAUNCH(K, T)                                                          \
     switch (mode) {                                                                   \
@@ -705,7 +695,7 @@ void spmv_xs(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const S
     default: fail(AMG_ERR_UNSUPPORTED, "x-staged SELL: unsupported SpMV epilogue"); \
     }
     const int64_t how = flag(FLAG_XS_PIPE);
-    if (how >= 2 && m.xs_maxw <= 7) FAMG_XS_LAUNCH(spmv_xs_burst_kernel, FAMG_COMMA 7)
+    if (how >= 2 && m.xs.maxw <= 7) FAMG_XS_LAUNCH(spmv_xs_burst_kernel, FAMG_COMMA 7)
     else if (how >= 2) FAMG_XS_LAUNCH(spmv_xs_burst_kernel, FAMG_COMMA 8)
     else if (how == 1) FAMG_XS_LAUNCH(spmv_xs_pipe_kernel, )
     else FAMG_XS_LAUNCH(spmv_xs_kernel, )

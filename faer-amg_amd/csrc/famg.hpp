@@ -924,6 +924,8 @@ CsrPtr sa_tentative_block(Ctx *ctx, int64_t nnodes, int64_t bs, const int64_t *a
                           const double *nn, int64_t ld, int64_t k, int64_t cd, double *coarse_nn);
 // block_jacobi P smoothing (interpolation/mod.rs:963-1028)
 CsrPtr block_jacobi_smooth(CsrOp &A, const CsrOp &P, int64_t bs, double omega);
+// create_weights (examples/amg/main.rs:571-580): w_c = 1 / (v_c^T A v_c), near-null on the host
+std::vector<double> default_weights(CsrOp &A, const double *nn, int64_t ld, int64_t k);
 // coarse near-null post-processing for k columns (hierarchy.rs:219-228)
 void nn_postprocess(CsrOp &A, int64_t iters, double *x, int64_t ld, int64_t k);
 struct SaConfig {

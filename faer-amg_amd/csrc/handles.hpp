@@ -31,6 +31,14 @@ amg_status set_last_error(amg_status s, const char *msg);
 // copy launch records into the caller's amg_launch_rec array (cycle plans)
 void export_plan(const std::vector<LaunchRec> &plan, amg_launch_rec *recs, int64_t cap, int64_t *count);
 
+// the CSR matrix behind a handle (AMG_ERR_INVALID for a null handle or another kind)
+inline CsrPtr need_csr_handle(const amg_linop *h) {
+    FAMG_REQUIRE(h && h->op, AMG_ERR_INVALID, "null amg_linop handle");
+    auto p = std::dynamic_pointer_cast<CsrOp>(h->op);
+    FAMG_REQUIRE(p, AMG_ERR_INVALID, "operator is not a CSR matrix");
+    return p;
+}
+
 template <typename F> amg_status guard(F &&f) {
     try {
         f();

@@ -629,7 +629,7 @@ struct SaStageClock {
 };
 
 // create_weights (examples/amg/main.rs:571-580): w_c = 1 / (v_c^T A v_c)
-static std::vector<double> default_weights(CsrOp &A, const double *nn, int64_t ld, int64_t k) {
+std::vector<double> default_weights(CsrOp &A, const double *nn, int64_t ld, int64_t k) {
     Ctx &ctx = *A.ctx;
     hipStream_t s = ctx.stream;
     const int64_t n = A.nrows;

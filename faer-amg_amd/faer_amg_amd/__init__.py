@@ -228,6 +228,14 @@ SIGNATURES = {
     "amg_block_cg_solve": (i32, [vp, vp, vp, i64, vp, i64, i64, i64, dbl, dbl, dbl, vp, i64, vp, P(i64)]),
     "amg_block_gram": (i32, [vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, vp]),
     "amg_block_gemm_update": (i32, [vp, vp, i64, vp, i64, vp, i64, i64, i64, i32]),
+    "amg_classical_config_default": (i32, [vp]),
+    "amg_cr_mis": (i32, [vp, vp, vp, P(i64)]),
+    "amg_cr_split": (i32, [vp, vp, vp, vp, vp, P(i64), vp]),
+    "amg_classical_build": (i32, [vp, vp, i64, i64, vp, vp, P(vp), vp]),
+    "amg_ls_candidates": (i32, [vp, vp, i64, P(vp)]),
+    "amg_ls_search": (i32, [vp, vp, vp, i64, i64, vp, i64, i32, i64, vp, vp, vp, vp, vp]),
+    "amg_ls_accept": (i32, [i64, vp, i64, i64, vp, i64, dbl, vp, vp, vp]),
+    "amg_ls_interpolation": (i32, [vp, vp, vp, i64, i64, vp, vp, P(vp), vp, vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -1075,6 +1083,174 @@ def get_sa_partitioner():
     c = PartitionerConfig()
     _ck(_lib.amg_get_sa_partitioner(C.byref(v), C.byref(c)))
     return v.value, c
+
+
+class ClassicalConfig(C.Structure):
+    """amg_classical_config: LeastSquaresConfig + CompatibleRelaxationConfig
+    (interpolation/mod.rs) + the hierarchy fields of SaConfig + where the search runs."""
+    _fields_ = [("search_depth", i64), ("depth_ls", i64), ("max_interp", i64), ("tau_threshold", dbl),
+                ("target_convergence", dbl), ("relax_steps", i64), ("smoother_coarsening_factor", dbl),
+                ("max_cr_iters", i64), ("coarsest_dim", i64), ("max_levels", i64), ("omega", dbl),
+                ("smoother", i32), ("chebyshev_steps", i32), ("where", i32), ("reserved", i32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _ck(_lib.amg_classical_config_default(C.byref(self)))
+        for k, v in kw.items():
+            if k == "smoother" and isinstance(v, str):
+                v = SMOOTHERS[v]
+            if k == "where" and isinstance(v, str):
+                v = SA_SETUP[v]
+            setattr(self, k, v)
+
+
+def cr_mis(G, candidates):
+    """amg_cr_mis: the C-points a compatible-relaxation round adds -- the greedy
+    independent set of the strength graph G (scipy CSR) among the candidates (n
+    booleans), by descending candidate degree, ties to the smaller index.  The chosen
+    nodes in the order chosen."""
+    G = G.tocsr()
+    n = G.shape[0]
+    mask = np.ascontiguousarray(np.asarray(candidates).astype(bool), np.uint8)
+    if mask.shape != (n,):
+        raise ValueError("one candidate flag per node")
+    tmp = HostCsr(_host_csr_from_scipy(G))
+    out = np.zeros(max(n, 1), np.int64)
+    nn_ = i64()
+    _ck(_lib.amg_cr_mis(tmp.h, mask.ctypes.data_as(vp), out.ctypes.data_as(vp), C.byref(nn_)))
+    return out[:nn_.value].copy()
+
+
+CR_STOP = {1: "converged", 2: "no_new_c", 3: "max_cr_iters", 4: "zero_vector"}
+
+
+def cr_split(A, G, **config):
+    """amg_cr_split: the compatible-relaxation C/F split of A with the strength graph G
+    (scipy CSR): (point_type (0 F, 1 C, 2 N), n_coarse, info) -- info: rounds, reduction,
+    stop (a CR_STOP name), c_per_round, c_round (per node: the round that made it a
+    C-point, else -1).  config: ClassicalConfig fields (target_convergence, relax_steps,
+    smoother_coarsening_factor, max_cr_iters)."""
+    cfg = ClassicalConfig(**config)
+    G = G.tocsr()
+    n = A.nrows
+    tmp = HostCsr(_host_csr_from_scipy(G))
+    pt = np.zeros(max(n, 1), np.int8)
+    cround = np.zeros(max(n, 1), np.int32)
+    nc = i64()
+    info = np.zeros(3 + max(int(cfg.max_cr_iters), 0))
+    _ck(_lib.amg_cr_split(A.h, tmp.h, C.byref(cfg), pt.ctypes.data_as(vp), cround.ctypes.data_as(vp), C.byref(nc),
+                          info.ctypes.data_as(vp)))
+    rounds = int(info[0])
+    return pt[:n], nc.value, {"rounds": rounds, "reduction": float(info[1]), "stop": CR_STOP.get(int(info[2])),
+                              "c_per_round": [int(v) for v in info[3:3 + rounds]], "c_round": cround[:n]}
+
+
+CLASSICAL_INFO_LEVELS = 32
+_CLASSICAL_LEVEL = ("rows", "coarse_rows", "cr_rounds", "longest_list", "device_rows", "host_rows", "empty_rows")
+
+
+def classical_build(A, near_null, weights=None, **config):
+    """amg_classical_build: the classical hierarchy (compatible relaxation + least-squares
+    interpolation; Hierarchy::coarsen with InterpolationConfig::Classical) as a Multigrid.
+    near_null: n x k; weights: k strength weights (None: 1 / v^T A v); config:
+    ClassicalConfig fields.  The result's classical_info lists, per coarsening, rows,
+    coarse_rows, cr_rounds, longest_list, device_rows, host_rows (rows whose search ran
+    on the host: with where 1 the lists beyond the kernel's cap) and empty_rows."""
+    cfg = ClassicalConfig(**config)
+    nn = _colmajor_host(near_null, A.nrows)
+    w = None if weights is None else np.ascontiguousarray(weights, np.float64)
+    h = vp()
+    info = np.zeros(1 + 7 * CLASSICAL_INFO_LEVELS, np.int64)
+    _ck(_lib.amg_classical_build(A.h, nn.ctypes.data_as(vp), nn.shape[0], nn.shape[1],
+                                 None if w is None else w.ctypes.data_as(vp), C.byref(cfg), C.byref(h),
+                                 info.ctypes.data_as(vp)))
+    mg = Multigrid._from_handle(h, A.ctx)
+    mg.classical_info = [dict(zip(_CLASSICAL_LEVEL, (int(v) for v in info[1 + 7 * l:8 + 7 * l])))
+                         for l in range(min(int(info[0]), CLASSICAL_INFO_LEVELS))]
+    return mg
+
+
+def ls_candidates(A, point_type, depth):
+    """amg_ls_candidates: per non-C row the C-points (point_type 1) within BFS depth
+    `depth` of the pattern of A, ascending, as a scipy CSR of unit values."""
+    pt = np.ascontiguousarray(point_type, np.int8)
+    if pt.shape != (A.nrows,):
+        raise ValueError("one point type per row")
+    h = vp()
+    _ck(_lib.amg_ls_candidates(A.h, pt.ctypes.data_as(vp), int(depth), C.byref(h)))
+    return HostCsr(h).to_scipy()
+
+
+def ls_search(lists, near_null, weights, max_interp=3, where=0, ctx=None, max_list=0):
+    """amg_ls_search: the best interpolation subset of each size 1..max_interp for every
+    row of `lists` (scipy CSR n x n, columns = candidate C-points).  where: 0 / 'host'
+    or 1 / 'device' (needs ctx).  Returns (count (n, mi) int32, cols (n, mi, mi) int64,
+    w (n, mi, mi), err (n, mi), info) -- the same bits on either path; info: device_rows,
+    host_rows, longest_list, subsets."""
+    lists = lists.tocsr()
+    lists.sort_indices()
+    n = lists.shape[0]
+    nn = _colmajor_host(near_null, n)
+    k = nn.shape[1]
+    wts = np.ascontiguousarray(weights, np.float64)
+    if len(wts) != k:
+        raise ValueError("one weight per near-null column")
+    mi = int(max_interp)
+    m = max(mi, 1)
+    count = np.zeros((max(n, 1), m), np.int32)
+    cols = np.zeros((max(n, 1), m, m), np.int64)
+    w = np.zeros((max(n, 1), m, m), np.float64)
+    err = np.zeros((max(n, 1), m), np.float64)
+    info = np.zeros(4, np.int64)
+    tmp = HostCsr(_host_csr_from_scipy(lists))
+    where = SA_SETUP[where] if isinstance(where, str) else int(where)
+    _ck(_lib.amg_ls_search(None if ctx is None else ctx.h, tmp.h, nn.ctypes.data_as(vp), nn.shape[0], k,
+                           wts.ctypes.data_as(vp), mi, where, int(max_list), count.ctypes.data_as(vp),
+                           cols.ctypes.data_as(vp), w.ctypes.data_as(vp), err.ctypes.data_as(vp),
+                           info.ctypes.data_as(vp)))
+    return count[:n], cols[:n], w[:n], err[:n], {"device_rows": int(info[0]), "host_rows": int(info[1]),
+                                                 "longest_list": int(info[2]), "subsets": int(info[3])}
+
+
+def ls_accept(near_null, weights, count, err, tau=1.2):
+    """amg_ls_accept: the accepted size per row (0: an empty row) from ls_search's count
+    and err by the reference's rule err_r < pow(accepted err, tau * (r - accepted size))."""
+    count = np.ascontiguousarray(count, np.int32)
+    err = np.ascontiguousarray(err, np.float64)
+    n, mi = count.shape
+    nn = _colmajor_host(near_null, n)
+    wts = np.ascontiguousarray(weights, np.float64)
+    chosen = np.zeros(max(n, 1), np.int32)
+    _ck(_lib.amg_ls_accept(n, nn.ctypes.data_as(vp), nn.shape[0], nn.shape[1], wts.ctypes.data_as(vp), mi,
+                           float(tau), count.ctypes.data_as(vp), err.ctypes.data_as(vp), chosen.ctypes.data_as(vp)))
+    return chosen[:n]
+
+
+def ls_interpolation(A, point_type, near_null, weights, **config):
+    """amg_ls_interpolation: classical interpolation for a given C/F split (point_type: 0
+    F, 1 C, 2 N): (P, coarse near-null (n_coarse x k), row_err).  config: ClassicalConfig
+    fields (depth_ls, search_depth, max_interp, tau_threshold, where).  P.ls_info: device_rows,
+    host_rows, longest_list, subsets, empty_rows of the search."""
+    cfg = ClassicalConfig(**config)
+    pt = np.ascontiguousarray(point_type, np.int8)
+    if pt.shape != (A.nrows,):
+        raise ValueError("one point type per row")
+    nn = _colmajor_host(near_null, A.nrows)
+    k = nn.shape[1]
+    wts = np.ascontiguousarray(weights, np.float64)
+    if len(wts) != k:
+        raise ValueError("one weight per near-null column")
+    nc = int((pt == 1).sum())
+    cnn = np.zeros((max(nc, 1), k), order="F")
+    rerr = np.zeros(max(A.nrows, 1))
+    h = vp()
+    info = np.zeros(5, np.int64)
+    _ck(_lib.amg_ls_interpolation(A.h, pt.ctypes.data_as(vp), nn.ctypes.data_as(vp), nn.shape[0], k,
+                                  wts.ctypes.data_as(vp), C.byref(cfg), C.byref(h), cnn.ctypes.data_as(vp),
+                                  rerr.ctypes.data_as(vp), info.ctypes.data_as(vp)))
+    P_ = SparseMatOp(h, A.ctx)
+    P_.ls_info = dict(zip(("device_rows", "host_rows", "longest_list", "subsets", "empty_rows"), (int(v) for v in info)))
+    return P_, cnn[:nc], rerr[:A.nrows]
 
 
 def _host_csr_from_scipy(G):

@@ -664,6 +664,134 @@ amg_status amg_partition_modularity_device(const amg_linop *graph, const amg_par
 amg_status amg_set_sa_partitioner(int32_t kind, const amg_partitioner_config *cfg);
 amg_status amg_get_sa_partitioner(int32_t *kind, amg_partitioner_config *cfg);
 
+/* ---- classical coarsening: the least-squares interpolation search --------------
+ * InterpolationConfig::Classical (interpolation/mod.rs:56-60): least_squares
+ * (:539-728) picks C-points by compatible relaxation and gives every other row
+ * the weights of a small constrained least-squares search over subsets of the
+ * C-points near it.  Scalar matrices only (the reference's "TODO: handle
+ * fine_mat.block_size?", :553).  The pieces below; DESIGN.md 18 has what is and
+ * is not built.  amg_classical_config carries the reference's defaults
+ * (LeastSquaresConfig, CompatibleRelaxationConfig) and the hierarchy fields of
+ * amg_sa_config. */
+typedef struct amg_classical_config {
+    int64_t search_depth;       /* strength graph / MIS depth; reference 3, default here 1 (a depth-3 row has ~1000 dofs in 3-D) */
+    int64_t depth_ls;           /* 2: candidates come from BFS depth depth_ls + search_depth */
+    int64_t max_interp;         /* 3 (<= 4) */
+    double tau_threshold;       /* 1.2 */
+    double target_convergence;  /* 0.3 */
+    int64_t relax_steps;        /* 5 */
+    double smoother_coarsening_factor; /* 256: CR's BlockSmoother partition */
+    int64_t max_cr_iters;       /* 20: guard, no reference counterpart */
+    int64_t coarsest_dim;       /* 1000, as amg_sa_config */
+    int64_t max_levels;         /* 0 = unlimited */
+    double omega;               /* 0.66 */
+    int32_t smoother;           /* 1 (L1), as amg_sa_config */
+    int32_t chebyshev_steps;    /* 0 */
+    int32_t where;              /* the search: 0 host, 1 device (default) */
+    int32_t reserved;
+} amg_classical_config;
+amg_status amg_classical_config_default(amg_classical_config *cfg);
+/* maximal_independent_set with a candidate mask (partitioners/mod.rs:395-423):
+ * candidates = n bytes (non-zero: a candidate; the reference's f_points).  The
+ * degree of a candidate is the sum, in stored order from 0.0, of its row's
+ * weights to neighbours that are candidates; the sweep runs by descending degree,
+ * ties to the smaller index (the pin of the reference's unstable sort); a chosen
+ * node clears itself and every node its row lists.  c_points: room for n entries,
+ * filled with the *n_new chosen nodes in the order chosen.  The mask is not
+ * changed.  AMG_ERR_DIM for a non-square graph. */
+amg_status amg_cr_mis(const amg_host_csr *graph, const uint8_t *candidates, int64_t *c_points, int64_t *n_new);
+/* The compatible-relaxation C/F split (least_squares, interpolation/mod.rs:574-652)
+ * of A with the strength graph `graph` (amg_strength_graph at cfg->search_depth;
+ * square, ascending columns, no self loops).  Every round: the points labelled F
+ * are the candidates of amg_cr_mis and the chosen ones become C; u_0 = the vector
+ * of ones (not the near-null) times I_f (1 on F and N points, 0 on C points);
+ * A_f = I_f A I_f with the C diagonals set to 1; relax_steps error-propagation
+ * steps u <- u - M_f (A_f u) with M_f the BlockSmoother of A_f over the modularity
+ * partition of `graph` at smoother_coarsening_factor (rebuilt every round);
+ * reduction = (|u_end|_2 / |u_start|_2)^(1 / relax_steps), tol = 1 - reduction;
+ * sigma_i = |u_i| / |u|_inf > tol labels i F, otherwise an F point becomes N.  The
+ * loop ends when reduction <= target_convergence.  The reference builds a second
+ * strength graph at depth 3 for the partition (partitioners/mod.rs:289-292); here
+ * `graph` serves both, which is the same at the reference's search_depth = 3.
+ * The relaxations run on the device, the relabelling on the host.  Guards the
+ * reference lacks: a round whose MIS adds no C-point ends the loop, so does
+ * max_cr_iters, a relaxed vector of zeros (or no F point left) counts as
+ * reduction 0, and a C-point stays a C-point when the reduction is above 1.
+ * point_type: n host entries, 0 F, 1 C, 2 N; c_round (may be NULL): n entries, the
+ * round (from 0) that made a node a C-point, else -1; *n_coarse the C count; info
+ * (may be NULL): 3 + max_cr_iters doubles = {rounds run, last reduction, stop
+ * reason (1 converged, 2 no new C-point, 3 max_cr_iters, 4 zero vector), the C
+ * count after each round (0 past the last)}. */
+amg_status amg_cr_split(amg_linop *A, const amg_host_csr *graph, const amg_classical_config *cfg, int8_t *point_type,
+                        int32_t *c_round, int64_t *n_coarse, double *info);
+/* Hierarchy::coarsen (hierarchy.rs:190-248) for InterpolationConfig::Classical:
+ * per level the strength graph at search_depth (host), amg_cr_split,
+ * amg_ls_interpolation, R = P^T and A_c = R (A P) by the device SpGEMMs, and the
+ * coarse near-null through amg_nn_postprocess (3 L1 steps, thin QR); the fine
+ * weights (NULL: create_weights, 1 / v^T A v) are used on every level.  Coarsening
+ * stops at coarsest_dim or max_levels, or when a level does not shrink.  Returns
+ * an ordinary multigrid: cfg->smoother on every level but the coarsest (0 Jacobi,
+ * 1 L1, 2 SGS, 4 Chebyshev; 3 has no aggregates here: AMG_ERR_UNSUPPORTED), the
+ * Cholesky coarse solve on the last.  FAMG_SA_LOG=1 prints a line per level with
+ * the stage times (graph, CR with its rounds, candidate lists, search, RAP).
+ * level_info (may be NULL): 1 + 7 * AMG_CLASSICAL_INFO_LEVELS host entries = {the
+ * coarsenings run, then per coarsening (the first AMG_CLASSICAL_INFO_LEVELS): rows,
+ * coarse rows, CR rounds, the longest candidate list, rows searched on the device,
+ * rows searched on the host (with where 1: lists beyond the kernel's cap -- on the
+ * levels below the fine one the Galerkin fill-in makes these the rule, DESIGN.md
+ * 18), empty rows of P}. */
+#define AMG_CLASSICAL_INFO_LEVELS 32
+amg_status amg_classical_build(amg_linop *A, const double *near_null, int64_t ld, int64_t k, const double *weights,
+                               const amg_classical_config *cfg, amg_linop **mg_out, int64_t *level_info);
+/* Candidate lists: for every row i with point_type[i] != 1 the C-points
+ * (point_type 1; 0 F, 2 N) of extract_local_subgraph(pattern(A), i, depth)
+ * (partitioners/mod.rs:695-718; the centre is in the ball), ascending; the row of
+ * a C-point is empty.  A host CSR of n rows with unit values.  The BFS runs on
+ * the host over the downloaded pattern. */
+amg_status amg_ls_candidates(const amg_linop *A, const int8_t *point_type, int64_t depth, amg_host_csr **lists);
+/* ls_interp_weights (interpolation/mod.rs:433-510) without its acceptance rule:
+ * for every row i of `lists` (n rows; columns = the candidates, ascending) the
+ * best subset of each size r = 1..max_interp -- constrained_subset_qp (:387-431)
+ * over combinations(r) in lexicographic order, the first strictly smaller error
+ * winning.  near_null: n x k column-major (ld), host; weights: k host values (the
+ * diagonal Q).  Slot s = i * max_interp + r - 1: count[s] = r or 0 (no valid
+ * subset, or the list is shorter than r), cols[s * max_interp + t] the chosen
+ * candidates (matrix columns, ascending; -1 past count), w[...] their weights (0
+ * past count), err[s] the weighted squared error (0 where count is 0).
+ * where 0: OpenMP on the host (ctx may be NULL).  where 1: the gfx950 kernel, one
+ * wave per row, for rows whose list has at most max_list candidates (0: the
+ * kernel's cap, 256; values above it are cut to it) -- longer rows run the host
+ * function; AMG_ERR_UNSUPPORTED for k > 16.  Host and device share one arithmetic
+ * (csrc/ls_pinned.hpp) and return the same bits.  info4 (may be NULL) = {rows
+ * searched on the device, rows searched on the host, the longest list, subsets
+ * enumerated}.  AMG_ERR_UNSUPPORTED for max_interp > 4, AMG_ERR_INVALID for
+ * max_interp < 1, k < 1, ld < n, a list that is not ascending and in range or a
+ * non-finite near-null entry or weight. */
+amg_status amg_ls_search(amg_ctx *ctx, const amg_host_csr *lists, const double *near_null, int64_t ld, int64_t k,
+                         const double *weights, int64_t max_interp, int32_t where, int64_t max_list, int32_t *count,
+                         int64_t *cols, double *w, double *err, int64_t *info4);
+/* The acceptance rule of ls_interp_weights (:456-509) on amg_ls_search's output,
+ * on the host for both search paths (it calls libm pow): accepted starts empty
+ * with err = btb = the row's vf Q vf^T; size r replaces it when err_r <
+ * pow(accepted err, tau * (r - accepted size)).  A slightly negative accepted
+ * error makes pow NaN and nothing larger is accepted, as in the reference.
+ * chosen[i] = the accepted size (its slot is chosen[i] - 1) or 0: an empty row. */
+amg_status amg_ls_accept(int64_t n, const double *near_null, int64_t ld, int64_t k, const double *weights,
+                         int64_t max_interp, double tau, const int32_t *count, const double *err, int32_t *chosen);
+/* least_squares' level build after the C/F split (:654-715): P (n x n_coarse) with
+ * 1.0 at (c, coarse index of c) for the C-points (coarse indices by ascending
+ * fine index) and the accepted weights in the other rows -- a row with no C-point
+ * in reach or no valid subset stays empty, as in the reference; coarse_nn
+ * (n_coarse x k column-major, ld n_coarse, host) = the near-null rows of the
+ * C-points; row_err (n, may be NULL) = the accepted error of each row (btb for an
+ * empty row, 0 for a C-point).  Candidates from BFS depth cfg->depth_ls +
+ * cfg->search_depth, the search where cfg->where says.  info5 (may be NULL) = {rows
+ * searched on the device, rows searched on the host, the longest list, subsets
+ * enumerated, empty rows of P}. */
+amg_status amg_ls_interpolation(amg_linop *A, const int8_t *point_type, const double *near_null, int64_t ld,
+                                int64_t k, const double *weights, const amg_classical_config *cfg, amg_linop **P,
+                                double *coarse_nn, double *row_err, int64_t *info5);
+
 /* ---- near-null search (adaptivity.rs:264-390, 434-443) -------------------------
  * From a bare SPD matrix to the candidates amg_sa_build takes, on the device.
  * Blocks are column-major n x k with a leading dimension, 1 <= k <= 64

@@ -10,7 +10,8 @@
 // every C entry therefore accumulates its products in ascending k with fma,
 // exactly the order of the CPU oracle, so C is bitwise identical to it.
 // Transpose is count -> scan -> atomic scatter -> per-row sort (deterministic
-// output because sort keys are distinct).
+// output because sort keys are distinct): a rank sort in LDS for rows of up to
+// 8192 entries, out of place against a copy in HBM for longer ones.
 #include <algorithm>
 #include <cmath>
 
@@ -231,9 +232,13 @@ __global__ void k_t_fill(const int64_t *rp, const int32_t *col, const double *va
 }
 
 // per-row sort by column (workgroup per row): rank sort of distinct keys in
-// LDS; rows longer than TSORT_CAP fall back to a serial insertion sort
+// LDS; a row longer than TSORT_CAP is ranked out of place against the unsorted
+// copy of it in kc / vc (the whole col / val arrays, copied before the launch
+// and read through L2).  Keys are distinct, so either way the sorted row is unique.
 template <int TSORT_CAP, int TSORT_BS>
-__global__ __launch_bounds__(TSORT_BS) void k_row_sort(const int64_t *rp, int64_t m, int32_t *col, double *val) {
+__global__ __launch_bounds__(TSORT_BS) void k_row_sort(const int64_t *rp, int64_t m, int32_t *col, double *val,
+                                                       const int32_t *__restrict__ kc,
+                                                       const double *__restrict__ vc) {
     __shared__ int32_t sk[TSORT_CAP];
     __shared__ double sv[TSORT_CAP];
     const int lane = threadIdx.x;
@@ -251,14 +256,13 @@ __global__ __launch_bounds__(TSORT_BS) void k_row_sort(const int64_t *rp, int64_
                 val[s0 + r] = sv[u];
             }
             __syncthreads();
-        } else if (lane == 0) {
-            for (int64_t a = 1; a < len; a++) {
-                const int32_t k = col[s0 + a];
-                const double v = val[s0 + a];
-                int64_t b = a - 1;
-                while (b >= 0 && col[s0 + b] > k) { col[s0 + b + 1] = col[s0 + b]; val[s0 + b + 1] = val[s0 + b]; b--; }
-                col[s0 + b + 1] = k;
-                val[s0 + b + 1] = v;
+        } else {
+            for (int64_t u = lane; u < len; u += TSORT_BS) {
+                const int32_t key = kc[s0 + u];
+                int64_t r = 0;
+                for (int64_t v = 0; v < len; v++) r += kc[s0 + v] < key;
+                col[s0 + r] = key;
+                val[s0 + r] = vc[s0 + u];
             }
         }
     }
@@ -284,6 +288,8 @@ void transpose(const GpuCsr &A, GpuCsr &T) {
         hipLaunchKernelGGL(k_t_count, dim3((unsigned)ceil_div(A.nnz, 256)), dim3(256), 0, s,
                            A.col.get(), A.nnz, cnt.get());
     DevBuf<int64_t> rp(n + 1);
+    DevBuf<int32_t> kcopy;  // unsorted copy of T for rows beyond the LDS sort; lives until the finalize
+    DevBuf<double> vcopy;
     const int64_t nnz = scan_counts(reinterpret_cast<const int64_t *>(cnt.get()), rp.get(), n, ctx);
     FAMG_REQUIRE(nnz == A.nnz, AMG_ERR_INVALID, "transpose: count mismatch");
     csr_alloc(T, &ctx, n, A.nrows, nnz);
@@ -301,12 +307,19 @@ void transpose(const GpuCsr &A, GpuCsr &T) {
         FAMG_CHECK_HIP(hipMemcpyAsync(&maxlen, cnt.get() + n, sizeof(maxlen), hipMemcpyDeviceToHost, s));
         FAMG_CHECK_HIP(hipStreamSynchronize(s));
         const unsigned g = (unsigned)std::min<int64_t>(n, 4096);
-        if (maxlen <= 2048)
+        if (maxlen <= 2048) {
             hipLaunchKernelGGL((k_row_sort<2048, 64>), dim3(g), dim3(64), 0, s, T.rp64.get(), n,
-                               T.col.get(), T.val.get());
-        else
+                               T.col.get(), T.val.get(), (const int32_t *)nullptr, (const double *)nullptr);
+        } else {
+            if (maxlen > 8192) {  // rows beyond the LDS sort: ranked against a copy
+                kcopy.resize(nnz);
+                vcopy.resize(nnz);
+                FAMG_CHECK_HIP(hipMemcpyAsync(kcopy.get(), T.col.get(), nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+                FAMG_CHECK_HIP(hipMemcpyAsync(vcopy.get(), T.val.get(), nnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+            }
             hipLaunchKernelGGL((k_row_sort<8192, 256>), dim3(g), dim3(256), 0, s, T.rp64.get(), n,
-                               T.col.get(), T.val.get());
+                               T.col.get(), T.val.get(), kcopy.get(), vcopy.get());
+        }
     }
     FAMG_CHECK_HIP(hipGetLastError());
     csr_finalize(T);

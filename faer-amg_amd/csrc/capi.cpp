@@ -825,6 +825,20 @@ amg_status amg_multigrid_levels(const amg_linop *mg, int64_t *levels) {
     });
 }
 
+amg_status amg_sa_level_info(const amg_linop *mg, int64_t level, int64_t *out8) {
+    return guard([&] {
+        FAMG_REQUIRE(out8, AMG_ERR_INVALID, "null output");
+        FAMG_REQUIRE(level >= 0, AMG_ERR_INVALID, "level out of range");
+        auto m = need_mg(mg);
+        FAMG_REQUIRE(!m->sa_levels.empty(), AMG_ERR_INVALID, "the multigrid keeps no amg_sa_build record");
+        FAMG_REQUIRE(level < (int64_t)m->sa_levels.size(), AMG_ERR_INVALID, "level out of range");
+        const SaLevelInfo &L = m->sa_levels[level];
+        const int64_t v[8] = {L.n, L.block_size, L.nodes, L.aggregates, L.strength_edges, L.on_device, L.host_reason,
+                              L.longest_ball};
+        std::copy(v, v + 8, out8);
+    });
+}
+
 amg_status amg_multigrid_set_graph(amg_linop *mg, int32_t enable) {
     return guard([&] {
         auto m = need_mg(mg);

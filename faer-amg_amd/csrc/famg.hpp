@@ -602,8 +602,16 @@ struct LevelShape {
     SpmvEpi epi0, epic;    // fold: d*f of this level's f / df: d_c and where d_c f_c goes
 };
 
+// One coarsening step of sa_build (amg_sa_level_info): on_device = the strength graph
+// and the aggregation ran on the device; host_reason = why not (the SG_REASON codes);
+// longest_ball = the longest candidate list the device counted (0 when it did not look)
+struct SaLevelInfo {
+    int64_t n, block_size, nodes, aggregates, strength_edges, on_device = 0, host_reason = 0, longest_ball = 0;
+};
+
 struct MultigridOp : LinOp {
     std::vector<MgLevel> levels;
+    std::vector<SaLevelInfo> sa_levels;  // sa_build's record, one entry per coarsening step
     int64_t mu = 1, steps = 1;
     bool use_graph = true;
     bool sgs_residual_form = false;  // true: literal smooth() order (residual SpMV + SGS(r))
@@ -826,16 +834,39 @@ int64_t aggregate_mis(const StrengthGraph &G, std::vector<int64_t> &agg_of, int6
 int64_t aggregate_finish(int64_t n, std::vector<int64_t> &agg, const std::vector<int64_t> &size0,
                          const std::vector<int64_t> &singles, const int64_t *sbeg, const int64_t *send,
                          const int32_t *col, const double *w, std::vector<int64_t> &agg_of);
-// Where sa_build and find_near_null run the strength graph and the aggregation at
-// strength depth 1 (amg_set_sa_setup): 0 host (default), 1 device (sagraph.hip)
+// Where sa_build and find_near_null run the strength graph and the aggregation
+// (amg_set_sa_setup): 0 host (default), 1 device (sagraph.hip) at any strength depth
 extern int g_sa_setup;
-constexpr int64_t SG_MAX_ROW = 4096;  // off-diagonal entries of a dof row the device strength graph ranks
-// strength_graph at depth 1 on the device (nn a device block): the node-level graph
+constexpr int64_t SG_MAX_ROW = 4096;  // candidates of a dof row the device strength graph ranks (and the ball cap)
+// why a level's strength graph cannot run on the device (SaLevelInfo::host_reason)
+enum : int { SG_REASON_NONE = 0, SG_REASON_POLICY = 1, SG_REASON_BALL_CAP = 2, SG_REASON_BYTES = 3, SG_REASON_INDEX = 4 };
+// The BFS ball of every row of a square CSR pattern (sagraph.hip): row i lists what
+// extract_local_subgraph(pattern, i, depth) reaches over stored entries, without i,
+// columns ascending.  kept = sum over rows of the entries the strength graph keeps.
+struct BallPattern {
+    DevBuf<int64_t> rp;
+    DevBuf<int32_t> col;
+    int64_t entries = 0, longest = 0, wave_rows = 0, block_rows = 0, kept = 0;
+};
+// Returns an SG_REASON code: NONE with `out` filled; BALL_CAP for a ball beyond
+// SG_MAX_ROW members (out.longest then is a lower bound), INDEX for 2^31 or more ball
+// or kept entries, BYTES (only with check_bytes) when 4 B per ball entry + 8 B per row
+// pointer + 12 B per kept entry exceed max_bytes (0: half the free device memory).
+// Counts are filled in either case; rp / col only with NONE.
+int ball_pattern_device(const GpuCsr &m, int64_t depth, bool check_bytes, int64_t max_bytes, BallPattern &out);
+struct SgDeviceInfo {
+    int64_t longest_ball = 0, wave_rows = 0, block_rows = 0, ball_entries = 0, dof_entries = 0, node_edges = 0;
+    int reason = SG_REASON_NONE;
+};
+// strength_graph at `depth` on the device (nn a device block): the node-level graph
 // as a CSR without SpMV storage.  The weight is (t*t)*(t*t) where the host takes
-// std::pow(t, 4.0); everything else gives the host's bits.  A row beyond SG_MAX_ROW:
-// *too_long = true and a null result, or AMG_ERR_UNSUPPORTED when too_long is null.
+// std::pow(t, 4.0); everything else gives the host's bits.  Depth 1 ranks the
+// matrix rows, depth >= 2 the rows of ball_pattern_device (freed before the node
+// merge allocates).  A level that cannot run (info->reason: BALL_CAP, BYTES against
+// max_bytes, INDEX) gives a null result when `fallback`, else AMG_ERR_UNSUPPORTED.
+// At depth 1 longest_ball counts only rows beyond a wave's 256 and ball_entries is 0.
 CsrPtr strength_graph_device(const CsrOp &A, const double *nn, int64_t ld, int64_t k, const double *w, int64_t bs,
-                             bool *too_long);
+                             int64_t depth, int64_t max_bytes, SgDeviceInfo *info, bool fallback);
 // aggregate_mis of a device graph: the root / claim phase in bounded passes on the
 // device, the tail on the host; past max_passes (0: the default budget) the host
 // sweep on the downloaded graph.  The same result either way.  info4 (optional) =
@@ -934,9 +965,6 @@ struct SaConfig {
     double omega = 0.66;
     int smoother = 1;
     int chebyshev_steps = 0;  // smoother 4: steps per application (0 = ChebyConfig's default)
-};
-struct SaLevelInfo {
-    int64_t n, block_size, nodes, aggregates, strength_edges;
 };
 std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn, int64_t ld, int64_t k,
                                       const double *weights, const SaConfig &cfg, std::vector<SaLevelInfo> *info);

@@ -468,12 +468,11 @@ void find_near_null(const CsrPtr &A, double *X, int64_t ld, int64_t k, int64_t i
     create_weights(*A, B.get(), n, k, wts.data());
     std::vector<int64_t> agg;
     int64_t na = 0;
-    // amg_set_sa_setup(1) at depth 1: the basis stays on the device (sagraph.hip)
+    // amg_set_sa_setup(1): the basis stays on the device (sagraph.hip); a null graph
+    // (a ball beyond the cap, the byte budget, the index range) takes the host path
     CsrPtr Gd;
-    if (g_sa_setup == 1 && strength_depth == 1) {
-        bool too_long = false;
-        Gd = strength_graph_device(*A, B.get(), n, k, wts.data(), block_size, &too_long);
-    }
+    if (g_sa_setup == 1)
+        Gd = strength_graph_device(*A, B.get(), n, k, wts.data(), block_size, strength_depth, 0, nullptr, true);
     if (Gd) {
         B.release();
         na = g_sa_partitioner == 1 ? partition_modularity_device(Gd->m, g_sa_part_cfg, agg, nullptr)

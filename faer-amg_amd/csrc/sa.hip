@@ -662,6 +662,7 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
     std::vector<int64_t> bss{cfg.block_size};
     std::vector<std::vector<int64_t>> aggs;
     std::vector<int64_t> naggs;
+    std::vector<SaLevelInfo> sa_levels;
     int64_t cur_ld = A->nrows;
     std::vector<double> nn(A->nrows * k);
     for (int64_t c = 0; c < k; c++) std::memcpy(nn.data() + c * cur_ld, nn_in + c * ld, A->nrows * sizeof(double));
@@ -676,15 +677,17 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
         std::vector<int64_t> agg;
         int64_t na = 0, edges = 0, minfo[4] = {0, 0, 0, 0}, pinfo[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const bool modularity = g_sa_partitioner == 1;  // amg_set_sa_partitioner (partition_host.cpp)
-        // policy 1 at depth 1: both stages on the device, the graph staying there (a
-        // row beyond SG_MAX_ROW, like depth > 1, keeps the level on the host)
+        // policy 1: both stages on the device at any depth, the graph staying there (a
+        // candidate list beyond SG_MAX_ROW, the byte budget or the index range keeps
+        // the level on the host: sg.reason)
         CsrPtr Gd;
-        if (g_sa_setup == 1 && cfg.strength_depth == 1) {
+        SgDeviceInfo sg;
+        sg.reason = SG_REASON_POLICY;
+        if (g_sa_setup == 1) {
             DevBuf<double> nnd(std::max<int64_t>(1, n * k));
             FAMG_CHECK_HIP(hipMemcpy2DAsync(nnd.get(), n * sizeof(double), nn.data(), cur_ld * sizeof(double),
                                             n * sizeof(double), k, hipMemcpyHostToDevice, ctx->stream));
-            bool too_long = false;
-            Gd = strength_graph_device(*cur, nnd.get(), n, k, w.data(), bs, &too_long);
+            Gd = strength_graph_device(*cur, nnd.get(), n, k, w.data(), bs, cfg.strength_depth, 0, &sg, true);
         }
         const bool on_device = Gd != nullptr;
         if (on_device) {
@@ -722,13 +725,14 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
                 snprintf(part, sizeof(part), " rounds %lld maxpasses %lld improve %lld swaps %lld",
                          (long long)pinfo[0], (long long)pinfo[2], (long long)pinfo[4], (long long)pinfo[5]);
             fprintf(stderr,
-                    "famg sa level %lld: n %lld nodes %lld aggregates %lld edges %lld device %d passes %lld fallback %lld"
-                    "%s ms: strength %.3f aggregation %.3f tentative %.3f smoothing %.3f rap %.3f nearnull %.3f\n",
+                    "famg sa level %lld: n %lld nodes %lld aggregates %lld edges %lld device %d reason %d ball %lld"
+                    " passes %lld fallback %lld%s ms: strength %.3f aggregation %.3f tentative %.3f smoothing %.3f"
+                    " rap %.3f nearnull %.3f\n",
                     (long long)(level - 1), (long long)n, (long long)nnodes, (long long)na, (long long)edges,
-                    on_device ? 1 : 0, (long long)minfo[0], (long long)minfo[3], part, ms[0], ms[1], ms[2], ms[3],
-                    ms[4], ms[5]);
+                    on_device ? 1 : 0, sg.reason, (long long)sg.longest_ball, (long long)minfo[0], (long long)minfo[3],
+                    part, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
         }
-        if (info) info->push_back({n, bs, nnodes, na, edges});
+        sa_levels.push_back({n, bs, nnodes, na, edges, on_device ? 1 : 0, sg.reason, sg.longest_ball});
         aggs.push_back(std::move(agg));
         naggs.push_back(na);
         Rs.push_back(R);
@@ -764,6 +768,8 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
     auto mg = std::make_shared<MultigridOp>();
     mg->ctx = ctx;
     mg->nrows = mg->ncols = A->nrows;
+    if (info) *info = sa_levels;
+    mg->sa_levels = std::move(sa_levels);
     MgLevel L0;
     L0.A = A;
     L0.S = As.size() == 1 ? LinOpPtr(make_coarse_chol(*A)) : make_smoother(A, 0);

@@ -1,8 +1,12 @@
 // sagraph.hip -- the two O(nnz) / serial stages of the general SA setup on the
-// device (policy amg_set_sa_setup(1), strength depth 1): the strength graph and
+// device (policy amg_set_sa_setup(1), any strength depth): the strength graph and
 // the root / claim phase of the MIS aggregation.  DESIGN.md 10.
 //
 // Restated from the reference (paths relative to its root):
+//  * BFS balls        extract_local_subgraph (partitioners/mod.rs:695-718) minus
+//                     the centre, the candidates of a dof row at depth >= 2, as a
+//                     CSR with ascending columns (k_ball): the host sorts its
+//                     candidates by (d, j), so discovery order never shows
 //  * strength graph   AdjacencyList::new_ls_strength_graph
 //                     (partitioners/mod.rs:337-393), block reduction aggregate +
 //                     filter_diag (:294-301, :464-497) -- the arithmetic of
@@ -234,16 +238,259 @@ __global__ void k_sg_scale(double *val, int64_t nnz, double gmax) {
 
 static unsigned grid256(int64_t n) { return (unsigned)std::max<int64_t>(1, ceil_div(n, 256)); }
 
+// ------------------------------------------------------------ BFS balls
+
+constexpr int BALL_SUB = 16;  // lanes that walk one frontier member's row together
+
+// v joins the visited set `tab` (SLOTS words, -1 = free): true for the lane that
+// put it there.  Multiplicative hash (ids that differ by multiples of a power of two
+// spread), linear probing; the callers keep free slots in the table.
+template <int SLOTS>
+__device__ __forceinline__ bool ball_insert(int32_t *tab, int32_t v) {
+    static_assert((SLOTS & (SLOTS - 1)) == 0, "a power of two");
+    unsigned h = ((unsigned)v * 2654435761u) >> (32 - __builtin_ctz(SLOTS));
+    for (int p = 0; p < SLOTS; p++) {
+        const int32_t old = atomicCAS(&tab[h], -1, v);
+        if (old == -1) return true;
+        if (old == v) return false;
+        h = (h + 1) & (SLOTS - 1);
+    }
+    return false;
+}
+
+// The ball of one row per GROUP lanes (64: a wave, balls of <= CAP = 256 members,
+// four rows per workgroup; 256: the workgroup, rows from `rowlist`, CAP = 4096).
+// The visited set is a hash table in LDS; the member list (without the centre) is
+// appended through an LDS counter and is the BFS queue as well: level d is the
+// slice of it that level d - 1 appended.  A lane stops inserting once the counter
+// has passed CAP, so at most CAP + GROUP members and the centre are ever in the
+// table, which therefore never fills.
+// FILL = false: cnt[i] = the ball's size, *kept += what the strength graph keeps of
+// it, *maxlen = the longest; a ball beyond CAP goes on `longrows` (GROUP 64) or is
+// reported through *maxlen alone with cnt[i] = 0 (GROUP 256).
+// FILL = true: the members sorted ascending (rank by counting in a wave, a bitonic
+// network in the workgroup) into bcol[brp[i] ...); rows whose size is not in
+// (0, CAP] are another launch's.
+template <int GROUP, int CAP, int SLOTS, bool FILL>
+__global__ __launch_bounds__(256) void k_ball(const int64_t *rp, const int32_t *col, int depth, int64_t nrows,
+                                              const int32_t *rowlist, int64_t *cnt, int32_t *longrows,
+                                              unsigned int *nlong, unsigned long long *maxlen,
+                                              unsigned long long *kept, const int64_t *brp, int32_t *bcol) {
+    constexpr int RPB = 256 / GROUP;
+    static_assert(2 * SLOTS >= 3 * (CAP + GROUP + 1), "the table stays under two thirds full");
+    __shared__ int32_t tab[RPB][SLOTS];
+    __shared__ int32_t list[RPB][CAP];
+    __shared__ int scnt[RPB];
+    const int g = threadIdx.x / GROUP, t = threadIdx.x % GROUP;
+    for (int64_t base = (int64_t)blockIdx.x * RPB; base < nrows; base += (int64_t)gridDim.x * RPB) {
+        const int64_t q = base + g;
+        const int64_t i = q < nrows ? (rowlist ? (int64_t)rowlist[q] : q) : -1;
+        bool live = i >= 0;
+        int64_t len = 0;
+        if (FILL && live) {
+            len = brp[i + 1] - brp[i];
+            live = len > 0 && len <= CAP;
+        }
+        for (int s = t; s < SLOTS; s += GROUP) tab[g][s] = -1;
+        if (t == 0) scnt[g] = 0;
+        __syncthreads();
+        if (live && t == 0) ball_insert<SLOTS>(tab[g], (int32_t)i);
+        __syncthreads();
+        int lo = 0, hi = 0, c = 0;
+        bool more = live;  // this row's BFS still has a frontier and room
+        for (int d = 0; d < depth; d++) {
+            const int nf = d == 0 ? 1 : hi - lo;
+            if (more)
+                for (int f = t / BALL_SUB; f < nf; f += GROUP / BALL_SUB) {
+                    const int64_t u = d == 0 ? i : (int64_t)list[g][lo + f];
+                    const int64_t e1 = rp[u + 1];
+                    for (int64_t e = rp[u] + t % BALL_SUB; e < e1; e += BALL_SUB) {
+                        if (__hip_atomic_load(&scnt[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) > CAP) break;
+                        const int32_t v = col[e];
+                        if (ball_insert<SLOTS>(tab[g], v)) {
+                            const int pos = atomicAdd(&scnt[g], 1);
+                            if (pos < CAP) list[g][pos] = v;
+                        }
+                    }
+                }
+            __syncthreads();
+            c = scnt[g];
+            lo = hi;
+            hi = c < CAP ? c : CAP;
+            more = more && c <= CAP && hi > lo;
+            if (!__syncthreads_or(more)) break;
+        }
+        // the loop left through a barrier: c and the list are final for every lane
+        if constexpr (!FILL) {
+            if (live && t == 0) {
+                if (c <= CAP) {
+                    cnt[i] = c;
+                    if (c) atomicAdd(kept, (unsigned long long)(c / 2 > 1 ? c / 2 : 1));
+                    atomicMax(maxlen, (unsigned long long)c);
+                } else if (GROUP == 64) {
+                    cnt[i] = 0;
+                    longrows[atomicAdd(nlong, 1u)] = (int32_t)i;
+                } else {
+                    cnt[i] = 0;
+                    atomicMax(maxlen, (unsigned long long)c);
+                }
+            }
+        } else if constexpr (GROUP == 64) {
+            if (live && c == (int)len)
+                for (int u = t; u < c; u += GROUP) {
+                    const int32_t ju = list[g][u];
+                    int r = 0;
+                    for (int v = 0; v < c; v++) r += list[g][v] < ju ? 1 : 0;
+                    bcol[brp[i] + r] = ju;
+                }
+        } else {
+            // RPB == 1: live, c and len are the workgroup's
+            const bool ok = live && c == (int)len;
+            int m = 1;
+            while (m < c) m <<= 1;
+            if (ok) {
+                for (int u = c + t; u < m; u += GROUP) list[g][u] = INT32_MAX;
+                __syncthreads();
+                for (int kk = 2; kk <= m; kk <<= 1)
+                    for (int j = kk >> 1; j > 0; j >>= 1) {
+                        for (int u = t; u < m; u += GROUP) {
+                            const int x = u ^ j;
+                            if (x > u) {
+                                const int32_t a = list[g][u], b = list[g][x];
+                                if ((a > b) == ((u & kk) == 0)) {
+                                    list[g][u] = b;
+                                    list[g][x] = a;
+                                }
+                            }
+                        }
+                        __syncthreads();
+                    }
+                for (int u = t; u < c; u += GROUP) bcol[brp[i] + u] = list[g][u];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void k_ball_ones(double *val, int64_t nnz) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < nnz) val[e] = 1.0;
+}
+
+constexpr int BALL_WAVE_SLOTS = 1024, BALL_BLOCK_SLOTS = 8192;
+
+int ball_pattern_device(const GpuCsr &m, int64_t depth, bool check_bytes, int64_t max_bytes, BallPattern &out) {
+    FAMG_REQUIRE(m.nrows == m.ncols, AMG_ERR_DIM, "pattern ball: matrix must be square");
+    FAMG_REQUIRE(depth >= 1, AMG_ERR_INVALID, "pattern ball: depth must be >= 1");
+    FAMG_REQUIRE(max_bytes >= 0, AMG_ERR_INVALID, "pattern ball: negative byte budget");
+    Ctx &ctx = *m.ctx;
+    hipStream_t s = ctx.stream;
+    const int64_t n = m.nrows;
+    const int d = (int)std::min<int64_t>(depth, std::max<int64_t>(1, n));  // a BFS settles within n levels
+    out = BallPattern{};
+    DevBuf<int64_t> cnt(std::max<int64_t>(1, n));
+    DevBuf<int32_t> longrows(std::max<int64_t>(1, n));
+    DevBuf<unsigned long long> meta(3);  // {long rows (low 32 bits), longest ball, kept entries}
+    FAMG_CHECK_HIP(hipMemsetAsync(meta.get(), 0, 3 * sizeof(unsigned long long), s));
+    unsigned long long hmeta[3] = {0, 0, 0};
+    const unsigned gw = (unsigned)std::min<int64_t>(std::max<int64_t>(1, ceil_div(n, 4)), int64_t(1) << 20);
+    if (n) {
+        hipLaunchKernelGGL((k_ball<64, SG_WAVE_CAP, BALL_WAVE_SLOTS, false>), dim3(gw), dim3(256), 0, s, m.rp64.get(),
+                           m.col.get(), d, n, (const int32_t *)nullptr, cnt.get(), longrows.get(),
+                           reinterpret_cast<unsigned int *>(meta.get()), meta.get() + 1, meta.get() + 2,
+                           (const int64_t *)nullptr, (int32_t *)nullptr);
+        FAMG_CHECK_HIP(hipGetLastError());
+        FAMG_CHECK_HIP(hipMemcpyAsync(hmeta, meta.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+    }
+    const int64_t nlong = (int64_t)(hmeta[0] & 0xffffffffull);
+    if (nlong) {
+        hipLaunchKernelGGL((k_ball<256, SG_BLOCK_CAP, BALL_BLOCK_SLOTS, false>),
+                           dim3((unsigned)std::min<int64_t>(nlong, 65536)), dim3(256), 0, s, m.rp64.get(), m.col.get(),
+                           d, nlong, longrows.get(), cnt.get(), (int32_t *)nullptr, (unsigned int *)nullptr,
+                           meta.get() + 1, meta.get() + 2, (const int64_t *)nullptr, (int32_t *)nullptr);
+        FAMG_CHECK_HIP(hipGetLastError());
+    }
+    DevBuf<int64_t> brp(n + 1);
+    const int64_t entries = scan_counts(cnt.get(), brp.get(), n, ctx);  // synchronises
+    FAMG_CHECK_HIP(hipMemcpyAsync(hmeta, meta.get(), sizeof(hmeta), hipMemcpyDeviceToHost, s));
+    FAMG_CHECK_HIP(hipStreamSynchronize(s));
+    out.entries = entries;
+    out.longest = (int64_t)hmeta[1];
+    out.block_rows = nlong;
+    out.wave_rows = n - nlong;
+    out.kept = (int64_t)hmeta[2];
+    if (out.longest > SG_BLOCK_CAP) return SG_REASON_BALL_CAP;
+    if (entries >= (int64_t(1) << 31) || out.kept >= (int64_t(1) << 31)) return SG_REASON_INDEX;
+    if (check_bytes) {
+        int64_t budget = max_bytes;
+        if (budget == 0) {
+            size_t fr = 0, tot = 0;
+            FAMG_CHECK_HIP(hipMemGetInfo(&fr, &tot));
+            budget = (int64_t)(fr / 2);
+        }
+        if (4 * entries + 8 * (n + 1) + 12 * out.kept > budget) return SG_REASON_BYTES;
+    }
+    DevBuf<int32_t> bcol(std::max<int64_t>(1, entries));
+    if (n && entries) {
+        hipLaunchKernelGGL((k_ball<64, SG_WAVE_CAP, BALL_WAVE_SLOTS, true>), dim3(gw), dim3(256), 0, s, m.rp64.get(),
+                           m.col.get(), d, n, (const int32_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr,
+                           (unsigned int *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                           brp.get(), bcol.get());
+        if (nlong)
+            hipLaunchKernelGGL((k_ball<256, SG_BLOCK_CAP, BALL_BLOCK_SLOTS, true>),
+                               dim3((unsigned)std::min<int64_t>(nlong, 65536)), dim3(256), 0, s, m.rp64.get(),
+                               m.col.get(), d, nlong, longrows.get(), (int64_t *)nullptr, (int32_t *)nullptr,
+                               (unsigned int *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                               brp.get(), bcol.get());
+        FAMG_CHECK_HIP(hipGetLastError());
+    }
+    FAMG_CHECK_HIP(hipStreamSynchronize(s));  // the counts and the row list are released here
+    out.rp = std::move(brp);
+    out.col = std::move(bcol);
+    return SG_REASON_NONE;
+}
+
+static const char *sg_reason_text(int reason) {
+    switch (reason) {
+    case SG_REASON_BALL_CAP: return "device strength graph: a row has more than 4096 candidates";
+    case SG_REASON_BYTES: return "device strength graph: the ball pattern and the dof graph exceed the byte budget";
+    case SG_REASON_INDEX: return "device strength graph: 2^31 or more ball or kept entries";
+    default: return "device strength graph: unsupported";
+    }
+}
+
 CsrPtr strength_graph_device(const CsrOp &A, const double *nn, int64_t ld, int64_t k, const double *w, int64_t bs,
-                             bool *too_long) {
+                             int64_t depth, int64_t max_bytes, SgDeviceInfo *info, bool fallback) {
     FAMG_REQUIRE(A.nrows == A.ncols, AMG_ERR_DIM, "strength graph: matrix must be square");
     FAMG_REQUIRE(bs >= 1 && A.nrows % bs == 0, AMG_ERR_DIM, "strength graph: block size must divide n");
-    FAMG_REQUIRE(k >= 1 && ld >= A.nrows, AMG_ERR_INVALID, "strength graph: bad near-null block");
-    if (too_long) *too_long = false;
+    FAMG_REQUIRE(k >= 1 && ld >= A.nrows && depth >= 1 && max_bytes >= 0, AMG_ERR_INVALID,
+                 "strength graph: bad near-null block, depth or byte budget");
+    SgDeviceInfo local;
+    SgDeviceInfo &inf = info ? *info : local;
+    inf = SgDeviceInfo{};
+    auto cannot = [&](int reason) -> CsrPtr {
+        inf.reason = reason;
+        if (!fallback) fail(AMG_ERR_UNSUPPORTED, sg_reason_text(reason));
+        return nullptr;
+    };
     Ctx *ctx = A.ctx;
     hipStream_t s = ctx->stream;
     const GpuCsr &m = A.m;
     const int64_t n = A.nrows;
+    // depth >= 2: the candidates of a row are its BFS ball; the kernels below take
+    // them from the ball's rp / col exactly as depth 1 takes them from the matrix's
+    BallPattern ball;
+    if (depth > 1) {
+        const int reason = ball_pattern_device(m, depth, true, max_bytes, ball);
+        inf.longest_ball = ball.longest;
+        inf.wave_rows = ball.wave_rows;
+        inf.block_rows = ball.block_rows;
+        inf.ball_entries = ball.entries;
+        if (reason != SG_REASON_NONE) return cannot(reason);
+    }
+    const int64_t *crp = depth > 1 ? ball.rp.get() : m.rp64.get();
+    const int32_t *ccol = depth > 1 ? ball.col.get() : m.col.get();
     DevBuf<double> wd(k), vn(std::max<int64_t>(1, n));
     FAMG_CHECK_HIP(hipMemcpyAsync(wd.get(), w, k * sizeof(double), hipMemcpyHostToDevice, s));
     DevBuf<int64_t> cnt(std::max<int64_t>(1, n));
@@ -253,8 +500,8 @@ CsrPtr strength_graph_device(const CsrOp &A, const double *nn, int64_t ld, int64
     auto D = make_csr(ctx);  // the dof-level graph (the result when bs == 1)
     if (n) {
         hipLaunchKernelGGL(k_sg_vn, dim3(grid256(n)), dim3(256), 0, s, nn, ld, k, wd.get(), n, vn.get());
-        hipLaunchKernelGGL(k_sg_count, dim3(grid256(n)), dim3(256), 0, s, m.rp64.get(), m.col.get(), n, cnt.get(),
-                           longrows.get(), reinterpret_cast<unsigned int *>(meta.get()), meta.get() + 1);
+        hipLaunchKernelGGL(k_sg_count, dim3(grid256(n)), dim3(256), 0, s, crp, ccol, n, cnt.get(), longrows.get(),
+                           reinterpret_cast<unsigned int *>(meta.get()), meta.get() + 1);
         FAMG_CHECK_HIP(hipGetLastError());
     }
     DevBuf<int64_t> drp(n + 1);
@@ -263,30 +510,35 @@ CsrPtr strength_graph_device(const CsrOp &A, const double *nn, int64_t ld, int64
     FAMG_CHECK_HIP(hipMemcpyAsync(hmeta, meta.get(), sizeof(hmeta), hipMemcpyDeviceToHost, s));
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
     const int64_t nlong = (int64_t)(hmeta[0] & 0xffffffffull);
-    if ((int64_t)hmeta[1] > SG_BLOCK_CAP) {
-        if (too_long) {
-            *too_long = true;
-            return nullptr;
-        }
-        fail(AMG_ERR_UNSUPPORTED, "device strength graph: a row has more than 4096 off-diagonal entries");
+    if (depth == 1) {
+        inf.longest_ball = (int64_t)hmeta[1];
+        inf.wave_rows = n - nlong;
+        inf.block_rows = nlong;
     }
-    FAMG_REQUIRE(dnnz < (int64_t(1) << 31), AMG_ERR_UNSUPPORTED, "device strength graph: 2^31 or more kept entries");
+    inf.dof_entries = dnnz;
+    if ((int64_t)hmeta[1] > SG_BLOCK_CAP) return cannot(SG_REASON_BALL_CAP);
+    if (dnnz >= (int64_t(1) << 31)) return cannot(SG_REASON_INDEX);
     csr_alloc(D->m, ctx, n, n, dnnz);
     D->m.rp64 = std::move(drp);
     D->nrows = D->ncols = n;
     if (n) {
         const unsigned gw = (unsigned)std::min<int64_t>(ceil_div(n, 4), int64_t(1) << 20);
-        hipLaunchKernelGGL((k_sg_fill<64, SG_WAVE_CAP>), dim3(gw), dim3(256), 0, s, m.rp64.get(), m.col.get(), nn, ld, k,
-                           wd.get(), vn.get(), n, (const int32_t *)nullptr, D->m.rp64.get(), D->m.col.get(),
-                           D->m.val.get());
+        hipLaunchKernelGGL((k_sg_fill<64, SG_WAVE_CAP>), dim3(gw), dim3(256), 0, s, crp, ccol, nn, ld, k, wd.get(),
+                           vn.get(), n, (const int32_t *)nullptr, D->m.rp64.get(), D->m.col.get(), D->m.val.get());
         if (nlong)
             hipLaunchKernelGGL((k_sg_fill<256, SG_BLOCK_CAP>), dim3((unsigned)std::min<int64_t>(nlong, 65536)),
-                               dim3(256), 0, s, m.rp64.get(), m.col.get(), nn, ld, k, wd.get(), vn.get(), nlong,
-                               longrows.get(), D->m.rp64.get(), D->m.col.get(), D->m.val.get());
+                               dim3(256), 0, s, crp, ccol, nn, ld, k, wd.get(), vn.get(), nlong, longrows.get(),
+                               D->m.rp64.get(), D->m.col.get(), D->m.val.get());
         FAMG_CHECK_HIP(hipGetLastError());
+    }
+    if (depth > 1) {  // the ball goes before the node-level merge allocates
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+        ball.col.release();
+        ball.rp.release();
     }
     if (bs == 1) {
         FAMG_CHECK_HIP(hipStreamSynchronize(s));  // wd, vn and the row list are released here
+        inf.node_edges = dnnz;
         return D;
     }
     const int64_t nnodes = n / bs;
@@ -315,6 +567,7 @@ CsrPtr strength_graph_device(const CsrOp &A, const double *nn, int64_t ld, int64
     if (gnnz) hipLaunchKernelGGL(k_sg_scale, dim3(grid256(gnnz)), dim3(256), 0, s, G->m.val.get(), gnnz, gmax);
     FAMG_CHECK_HIP(hipGetLastError());
     FAMG_CHECK_HIP(hipStreamSynchronize(s));
+    inf.node_edges = gnnz;
     return G;
 }
 
@@ -569,8 +822,16 @@ amg_status amg_get_sa_setup(int32_t *where) {
 
 amg_status amg_strength_graph_device(const amg_linop *A, const double *near_null, int64_t ld, int64_t k,
                                      const double *weights, int64_t block_size, amg_mem mem, amg_linop **graph) {
+    return amg_strength_graph_device_depth(A, near_null, ld, k, weights, 1, block_size, mem, 0, graph, nullptr);
+}
+
+amg_status amg_strength_graph_device_depth(const amg_linop *A, const double *near_null, int64_t ld, int64_t k,
+                                           const double *weights, int64_t depth, int64_t block_size, amg_mem mem,
+                                           int64_t max_bytes, amg_linop **graph, int64_t *info6) {
     return guard([&] {
         FAMG_REQUIRE(graph, AMG_ERR_INVALID, "null output");
+        FAMG_REQUIRE(depth >= 1, AMG_ERR_INVALID, "strength graph: depth must be >= 1");
+        FAMG_REQUIRE(max_bytes >= 0, AMG_ERR_INVALID, "strength graph: negative byte budget");
         auto a = need_csr_sg(A);
         FAMG_REQUIRE(near_null && weights, AMG_ERR_INVALID, "null argument");
         FAMG_REQUIRE(mem == AMG_MEM_DEVICE || mem == AMG_MEM_HOST, AMG_ERR_INVALID, "bad amg_mem");
@@ -589,7 +850,44 @@ amg_status amg_strength_graph_device(const amg_linop *A, const double *near_null
             nn = stage.get();
             ldd = n;
         }
-        *graph = new amg_linop{strength_graph_device(*a, nn, ldd, k, weights, block_size, nullptr)};
+        SgDeviceInfo inf;
+        CsrPtr G = strength_graph_device(*a, nn, ldd, k, weights, block_size, depth, max_bytes, &inf, true);
+        if (info6) {
+            const int64_t v[6] = {inf.longest_ball, inf.wave_rows, inf.block_rows,
+                                  inf.ball_entries, inf.dof_entries, inf.node_edges};
+            std::copy(v, v + 6, info6);
+        }
+        if (!G) fail(AMG_ERR_UNSUPPORTED, sg_reason_text(inf.reason));
+        *graph = new amg_linop{G};
+    });
+}
+
+amg_status amg_pattern_ball_device(const amg_linop *A, int64_t depth, amg_linop **ball) {
+    return guard([&] {
+        FAMG_REQUIRE(ball, AMG_ERR_INVALID, "null output");
+        FAMG_REQUIRE(depth >= 1, AMG_ERR_INVALID, "pattern ball: depth must be >= 1");
+        auto a = need_csr_sg(A);
+        FAMG_REQUIRE(a->nrows == a->ncols, AMG_ERR_DIM, "pattern ball: matrix must be square");
+        a->ctx->set_device();
+        hipStream_t s = a->ctx->stream;
+        BallPattern b;
+        const int reason = ball_pattern_device(a->m, depth, false, 0, b);
+        FAMG_REQUIRE(reason != SG_REASON_BALL_CAP, AMG_ERR_UNSUPPORTED,
+                     "pattern ball: a ball has more than 4096 members");
+        FAMG_REQUIRE(reason == SG_REASON_NONE, AMG_ERR_UNSUPPORTED, "pattern ball: 2^31 or more entries");
+        const int64_t n = a->nrows;
+        auto B = make_csr(a->ctx);
+        csr_alloc(B->m, a->ctx, n, n, b.entries);
+        B->m.rp64 = std::move(b.rp);
+        B->nrows = B->ncols = n;
+        if (b.entries) {
+            FAMG_CHECK_HIP(hipMemcpyAsync(B->m.col.get(), b.col.get(), b.entries * sizeof(int32_t),
+                                          hipMemcpyDeviceToDevice, s));
+            hipLaunchKernelGGL(k_ball_ones, dim3(grid256(b.entries)), dim3(256), 0, s, B->m.val.get(), b.entries);
+            FAMG_CHECK_HIP(hipGetLastError());
+        }
+        FAMG_CHECK_HIP(hipStreamSynchronize(s));
+        *ball = new amg_linop{B};
     });
 }
 

@@ -183,6 +183,9 @@ SIGNATURES = {
     "amg_get_sa_setup": (i32, [P(i32)]),
     "amg_strength_graph_device": (i32, [vp, vp, i64, i64, vp, i64, C.c_int, P(vp)]),
     "amg_aggregate_mis_device": (i32, [vp, i64, vp, P(i64), vp]),
+    "amg_pattern_ball_device": (i32, [vp, i64, P(vp)]),
+    "amg_strength_graph_device_depth": (i32, [vp, vp, i64, i64, vp, i64, i64, C.c_int, i64, P(vp), vp]),
+    "amg_sa_level_info": (i32, [vp, i64, vp]),
     "amg_partitioner_config_default": (i32, [vp]),
     "amg_partition_modularity": (i32, [vp, vp, vp, P(i64), vp]),
     "amg_partition_modularity_device": (i32, [vp, vp, vp, P(i64), vp]),
@@ -831,6 +834,15 @@ class Multigrid(LinOp):
                  "mode": MODES.get(r.mode, "?"), "name": r.name.decode(), "rows": r.rows,
                  "bytes": r.bytes, "csr_bytes": r.csr_bytes} for r in recs[:n.value]]
 
+    def sa_level_info(self, level):
+        """amg_sa_level_info: the record smoothed_aggregation kept of coarsening step
+        `level` as 8 integers -- (n, block size, nodes, aggregates, strength edges,
+        built on the device 0/1, reason it stayed on the host, longest ball); reasons
+        0 none, 1 policy, 2 ball cap, 3 byte budget, 4 index range."""
+        out = np.zeros(8, np.int64)
+        _ck(_lib.amg_sa_level_info(self.h, int(level), out.ctypes.data_as(vp)))
+        return tuple(int(v) for v in out)
+
     def level(self, l):
         """(A, S, R, P) handles of level l (R, P None on the coarsest)."""
         a, s, r, p = vp(), vp(), vp(), vp()
@@ -968,9 +980,12 @@ SA_SETUP = {"host": 0, "device": 1}
 
 def set_sa_setup(where):
     """amg_set_sa_setup (process-wide): where amg_sa_build and amg_find_near_null run
-    the strength graph and the aggregation at strength depth 1 -- 'host' / 0 (default)
-    or 'device' / 1.  Not bitwise neutral: the device weighs an edge with (t*t)*(t*t)
-    where the host calls pow(t, 4.0)."""
+    the strength graph and the aggregation -- 'host' / 0 (default) or 'device' / 1, at
+    any strength depth (depth > 1: the BFS balls are built on the device too).  A level
+    whose candidate lists pass 4096, whose ball pattern passes half the free device
+    memory or 2^31 entries keeps the host path; Multigrid.sa_level_info says which.
+    Not bitwise neutral: the device weighs an edge with (t*t)*(t*t) where the host
+    calls pow(t, 4.0)."""
     _ck(_lib.amg_set_sa_setup(SA_SETUP[where] if isinstance(where, str) else int(where)))
 
 
@@ -980,11 +995,25 @@ def get_sa_setup():
     return v.value
 
 
-def strength_graph_device(A, near_null, weights, block_size=1):
-    """amg_strength_graph_device: the depth-1 node-level strength graph built on the
-    device, as a SparseMatOp without SpMV storage (read it with .arrays() /
+_SG_INFO = ("longest_ball", "wave_rows", "block_rows", "ball_entries", "dof_entries", "node_edges")
+
+
+def pattern_ball_device(A, depth):
+    """amg_pattern_ball_device: the BFS ball of every row of A's pattern (depth >= 1,
+    stored entries only, without the row itself, columns ascending) as a SparseMatOp
+    with unit values and no SpMV storage.  AmgError status 3 for a ball beyond 4096."""
+    h = vp()
+    _ck(_lib.amg_pattern_ball_device(A.h, int(depth), C.byref(h)))
+    return SparseMatOp(h, A.ctx)
+
+
+def strength_graph_device(A, near_null, weights, block_size=1, depth=1, max_bytes=0, info=False):
+    """amg_strength_graph_device_depth: the node-level strength graph at `depth` built
+    on the device, as a SparseMatOp without SpMV storage (read it with .arrays() /
     .to_scipy(), pass it to aggregate_mis_device).  near_null: n x k, numpy or a
-    column-major torch tensor (host or device)."""
+    column-major torch tensor (host or device).  max_bytes: the budget of the ball
+    pattern plus the dof graph at depth > 1 (0: half the free device memory).
+    info=True: (graph, dict of _SG_INFO)."""
     if isinstance(near_null, np.ndarray):
         near_null = _colmajor_host(near_null, A.nrows)
     p, m, n, k, ld = _dptr(near_null)
@@ -995,8 +1024,11 @@ def strength_graph_device(A, near_null, weights, block_size=1):
         raise ValueError("one weight per near-null column")
     h = vp()
     with _ordered(A.ctx, m):
-        _ck(_lib.amg_strength_graph_device(A.h, p, ld, k, w.ctypes.data_as(vp), block_size, m, C.byref(h)))
-    return SparseMatOp(h, A.ctx)
+        i6 = np.zeros(6, np.int64)
+        _ck(_lib.amg_strength_graph_device_depth(A.h, p, ld, k, w.ctypes.data_as(vp), int(depth), block_size, m,
+                                                 int(max_bytes), C.byref(h), i6.ctypes.data_as(vp)))
+    G = SparseMatOp(h, A.ctx)
+    return (G, dict(zip(_SG_INFO, (int(v) for v in i6)))) if info else G
 
 
 def aggregate_mis_device(G, max_passes=0):

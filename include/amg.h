@@ -574,12 +574,16 @@ amg_status amg_nn_postprocess(const amg_linop *A, int64_t iters, double *x, int6
  * are bitwise neutral and this is not -- the device weighs a kept edge with
  * (t*t)*(t*t) where the host calls pow(t, 4.0) (<= 2 ULP apart; no device code
  * reproduces libm's pow bit for bit), so a device-built hierarchy is an equally
- * valid SA hierarchy but not bit-identical to a host-built one.  A level keeps
- * the host path at strength_depth > 1 (the BFS neighbourhoods are host only) and
- * when a dof row has more than 4096 off-diagonal entries.  With the policy at 0
- * nothing changes anywhere.  AMG_ERR_INVALID for another value.
- * FAMG_SA_LOG=1 makes amg_sa_build print per-level, per-stage wall times to
- * stderr under either policy. */
+ * valid SA hierarchy but not bit-identical to a host-built one.  The policy holds
+ * at every strength_depth >= 1: at depth > 1 the candidates of a dof row are its
+ * BFS ball, built on the device (amg_pattern_ball_device).  A level keeps the host
+ * path when a candidate list has more than 4096 members (reason 2), when the ball
+ * pattern and the dof graph (4 B per ball entry, 8 B per row pointer, 12 B per kept
+ * entry) exceed half the free device memory (reason 3), or when the ball or the
+ * kept entries reach 2^31 (reason 4); amg_sa_level_info reports which.  With the
+ * policy at 0 nothing changes anywhere.  AMG_ERR_INVALID for another value.
+ * FAMG_SA_LOG=1 makes amg_sa_build print per-level, per-stage wall times, the
+ * longest ball and the reason to stderr under either policy. */
 amg_status amg_set_sa_setup(int32_t where);
 amg_status amg_get_sa_setup(int32_t *where);
 /* amg_strength_graph at depth 1 on the device (new_ls_strength_graph,
@@ -593,6 +597,47 @@ amg_status amg_get_sa_setup(int32_t *where);
 amg_status amg_strength_graph_device(const amg_linop *A, const double *near_null, int64_t ld, int64_t k,
                                      const double *weights, int64_t block_size, amg_mem mem,
                                      amg_linop **graph);
+/* The BFS ball of every row of the square CSR pattern of A: row i of *ball lists
+ * extract_local_subgraph(pattern, i, depth) (partitioners/mod.rs:695-718) without
+ * i itself, columns ascending, following stored entries only (an asymmetric
+ * pattern, a row without a diagonal; a row storing only its diagonal has an
+ * empty ball).  A device CSR handle with unit values and no SpMV storage: read
+ * it with amg_csr_download.  A wave builds a ball of <= 256 members (a hash
+ * table and the member list in LDS), a workgroup one of <= 4096.
+ * AMG_ERR_INVALID: depth < 1 or a null argument (nothing touched);
+ * AMG_ERR_DIM: A not square; AMG_ERR_UNSUPPORTED: a ball of more than 4096
+ * members (never truncated) or 2^31 or more entries. */
+amg_status amg_pattern_ball_device(const amg_linop *A, int64_t depth, amg_linop **ball);
+/* amg_strength_graph_device at any depth >= 1 (amg_strength_graph_device is depth
+ * 1).  Depth 1: exactly that function.  Depth >= 2: the candidates of a dof row
+ * are its ball (above) where depth 1 takes the row's off-diagonal entries; the
+ * ranking, merging and scaling are the same kernels, so the result equals the
+ * host's amg_strength_graph(depth) as depth 1 does.  The ball is freed before the
+ * node-level merge allocates.  max_bytes bounds the ball pattern plus the dof
+ * graph (4 B per ball entry, 8 B per row pointer, 12 B per kept entry); 0 = half
+ * the free device memory after the ball is counted.  info6 (may be NULL; written
+ * whenever the counts were taken) = {longest ball, rows on the wave ball kernel,
+ * rows on the workgroup ball kernel, ball entries, kept dof entries, node edges};
+ * at depth 1 no ball is built: the first three describe the ranking kernels (the
+ * longest row only where it passes 256) and ball entries is 0.
+ * AMG_ERR_INVALID: null graph, depth < 1 or max_bytes < 0 (nothing touched), null
+ * A / near_null / weights; AMG_ERR_UNSUPPORTED, the message naming the cause: a
+ * ball of more than 4096 members, the byte budget, 2^31 or more ball or kept
+ * entries. */
+amg_status amg_strength_graph_device_depth(const amg_linop *A, const double *near_null, int64_t ld, int64_t k,
+                                           const double *weights, int64_t depth, int64_t block_size,
+                                           amg_mem mem, int64_t max_bytes, amg_linop **graph, int64_t *info6);
+/* The record amg_sa_build kept of coarsening step `level` (0 = from the finest
+ * operator) in the multigrid it returned: out8 = {n, block size, nodes,
+ * aggregates, strength edges, strength graph and aggregation ran on the device
+ * (0/1), why they stayed on the host, longest ball}.  Reasons: 0 none (they ran on
+ * the device), 1 the policy (amg_set_sa_setup(0)), 2 a candidate list beyond 4096,
+ * 3 the byte budget, 4 the index range.  The longest ball is what the device
+ * counted before it decided: 0 under policy 0, a lower bound past the cap, at
+ * depth 1 the longest row only where it passes 256.  AMG_ERR_INVALID: null out8,
+ * a multigrid without such a record (built another way, or with one level), a
+ * level out of range. */
+amg_status amg_sa_level_info(const amg_linop *mg, int64_t level, int64_t *out8);
 /* amg_aggregate_mis (maximal_independent_set, partitioners/mod.rs:395-423) of a
  * square CSR handle -- a result of amg_strength_graph_device or a graph uploaded
  * with amg_csr_create: exactly the host's agg_of (host, n entries) and *naggs.

@@ -11,9 +11,12 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/amg.h"
@@ -125,6 +128,25 @@ struct Ctx {
 };
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Workgroups of `kernel` per CU at this block size and dyn bytes of dynamic LDS,
+// asked of the runtime once per (kernel, block, dyn); 1 when it cannot say.  The
+// marching kernels size one round of workgroups over the chip with it.
+inline int kernel_occupancy(const void *kernel, int block, size_t dyn) {
+    static std::mutex mu;
+    static std::map<std::tuple<const void *, int, size_t>, int> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    const auto key = std::make_tuple(kernel, block, dyn);
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, dyn) != hipSuccess || n < 1) {
+        (void)hipGetLastError();
+        n = 1;
+    }
+    cache[key] = n;
+    return n;
+}
 
 // Environment switches (FAMG_*, listed in INTEGRATION.md): every site reads its
 // switch once, into a static const, through one of these.

@@ -172,9 +172,6 @@ struct GtcStore {
     DevBuf<uint16_t> dict;  // nclass x ke entries: value index << 8 | step slot
     DevBuf<double> vtab;    // the distinct values (<= 256)
     int ke = 0, nce = 0, ntab = 0, nclass = 0;
-    // R: per class the first entry of each fine-plane group dz = -1, 0, 1, 2 and the
-    // real entry count (5 bytes; the marching fused restriction of fine.hip)
-    DevBuf<uint8_t> kdz;
     // R: per class its value at each of the 32 slots (dz, dy, dx) a 2 x 2 x 2 box
     // smoothed by the 7-point stencil reaches, +0.0 where the class has no entry
     // (fine.hip k_fine_rr); empty when some class has an entry outside them

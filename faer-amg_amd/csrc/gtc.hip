@@ -19,7 +19,6 @@
 // SET, ADD (y += P v_c), ADD0 (y = d*b + P v_c, the folded zero-guess step).
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <unordered_map>
 
 #include "famg.hpp"
@@ -512,18 +511,7 @@ bool gtc_attach(GpuCsr &m, const int64_t *fg, const int64_t *cg, int which) {
     FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc.cls.get(), cls.data(), cls.size(), hipMemcpyHostToDevice, s));
     FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc.dict.get(), hd.data(), hd.size() * 2, hipMemcpyHostToDevice, s));
     FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc.vtab.get(), vt.data(), vt.size() * 8, hipMemcpyHostToDevice, s));
-    if (is_r && ke <= 255) {  // per class: where each fine plane's entries start (slots ascend in dz)
-        std::vector<uint8_t> kdz(dict.size() * 5);
-        for (size_t c = 0; c < dict.size(); c++) {
-            int k = 0;
-            for (int g = 0; g < 4; g++) {
-                kdz[c * 5 + g] = (uint8_t)k;
-                while (k < (int)dict[c].size() && dict[c][k].first / 16 == g) k++;
-            }
-            kdz[c * 5 + 4] = (uint8_t)dict[c].size();
-        }
-        m.gtc.kdz.resize(kdz.size());
-        FAMG_CHECK_HIP(hipMemcpyAsync(m.gtc.kdz.get(), kdz.data(), kdz.size(), hipMemcpyHostToDevice, s));
+    if (is_r) {
         // the 32-slot weights (fine.hip k_fine_rr): every entry in the slots a
         // 2 x 2 x 2 box smoothed by the 7-point stencil reaches, else none
         static const int8_t pat[64] = {
@@ -586,25 +574,6 @@ static int gtc_tz() {
 static int gtc_rtz() {
     static const int v = env_char("FAMG_GTC_RTZ") == '4' ? 4 : 2;
     return v;
-}
-
-// workgroups of the marching R per CU with dyn bytes of dictionary (cached)
-static int gtc_march_occupancy(bool df, size_t dyn) {
-    static std::mutex mu;
-    static std::unordered_map<size_t, int> cache;
-    const size_t key = dyn * 2 + (df ? 1 : 0);
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    int n = 0;
-    const hipError_t e = df ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_gtc_restrict_march<true>, 256, dyn)
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_gtc_restrict_march<false>, 256, dyn);
-    if (e != hipSuccess || n < 1) {
-        (void)hipGetLastError();
-        n = 1;
-    }
-    cache[key] = n;
-    return n;
 }
 
 // ---- k-wide forms (spmm_gtc, the block V-cycle): kb columns per launch.  The
@@ -814,7 +783,9 @@ void spmv_gtc(const GpuCsr &m, const double *x, double *y, SpmvMode mode, const 
             // second, partial round left most CUs idle: 512 / 768 / 1024 / 1408
             // workgroups on R_0 of the 256^3 cycle ran 68 / 54 / 70 / 63 us)
             const size_t dyn = (size_t)a.nce * sizeof(uint16_t);
-            const int per_cu = gtc_march_occupancy(mode == SPMV_SETDF, dyn);
+            const void *march = mode == SPMV_SETDF ? reinterpret_cast<const void *>(k_gtc_restrict_march<true>)
+                                                   : reinterpret_cast<const void *>(k_gtc_restrict_march<false>);
+            const int per_cu = kernel_occupancy(march, 256, dyn);
             const int64_t want = (int64_t)per_cu * std::max(m.ctx->num_cus, 1);
             a.jper = (int)std::max<int64_t>(1, ceil_div((int64_t)(z1 - z0) * ntxy, want));
             a.mz0 = z0;

@@ -1,6 +1,6 @@
 """Workload for counter passes over the fused fine-level kernels (fine.hip):
-the C2 hierarchy (7-pt 256^3), then 10 launches of k_fine_resid_restrict and
-10 of k_fine_interp_jacobi exactly as the cycle makes them
+the C2 hierarchy (7-pt 256^3), then 10 launches of k_fine_rr and
+10 of k_fine_pj exactly as the cycle makes them
 (amg_multigrid_fine_launch), between k_trace_mark<<<1>>> and <<<2>>>."""
 import os
 import sys

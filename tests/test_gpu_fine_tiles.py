@@ -12,7 +12,9 @@ its path:
                  last 2 rows
   (66, 63, 51)   odd ny, nz on more than one tile in y
 The V-cycle with the fused launches is bitwise the unfused one (fine_fuse = 0)
-for the default run length and for runs of 2, 6 and 1000 planes."""
+for the default run length and for runs of 2, 6 and 1000 planes.  Last, a
+hierarchy whose transfers the fused kernels cannot take (trilinear P) runs the
+four-launch form."""
 import numpy as np
 import pytest
 
@@ -133,3 +135,71 @@ def test_fine_tiles_graph_replay(ctx):
         mg.set_graph(True)
     for z in zs:
         assert np.array_equal(bits(H(z)), bits(z0))
+
+
+def lin1d(n):
+    """Linear interpolation from the (n + 1) // 2 coarse points at the even fine
+    indices: weight 1 on them, 1/2 and 1/2 between two, the upper 1/2 dropped
+    where it would leave the coarse grid."""
+    import scipy.sparse as sp
+    x = np.arange(n)
+    ev, od = x[x % 2 == 0], x[x % 2 == 1]
+    rows = np.concatenate([ev, od, od])
+    cols = np.concatenate([ev // 2, od // 2, od // 2 + 1])
+    vals = np.concatenate([np.ones(ev.size), np.full(2 * od.size, 0.5)])
+    keep = cols < (n + 1) // 2
+    return sp.csr_matrix((vals[keep], (rows[keep], cols[keep])), shape=(n, (n + 1) // 2))
+
+
+def trilinear(dims):
+    import scipy.sparse as sp
+    nx, ny, nz = dims
+    return sp.kron(lin1d(nz), sp.kron(lin1d(ny), lin1d(nx))).tocsr()
+
+
+def test_fine_unfusable_transfers(ctx):
+    """The fusing predicates reject transfers the fused kernels cannot take.  A
+    three-level hierarchy on the 7-point Laplacian 64 x 32 x 32 (the smallest DIA
+    fine level with an even nx) with trilinear P, R = P^T and Galerkin coarse
+    operators: grids, frames, the constant stencil and the one-value d all pass,
+    but P's rows hold up to eight entries (k_fine_pj walks four) and R's reach
+    (dz, dy, dx) = (-1, -1, -1), outside the 32 slots of k_fine_rr's weights.  So
+    with fine_fuse = 1 the fine level takes the four-launch form (the plan names
+    neither fused launch), bitwise the fine_fuse = 0 cycle, and within 1e-11 of
+    the oracle's cycle over the same levels (test_fine_fused_bitwise's bound)."""
+    import oracle as O
+    F = fa()
+    dims = [(64, 32, 32), (32, 16, 16), (16, 8, 8)]
+    A = [F.SparseMatOp.laplace3d_7pt(ctx, *dims[0])]
+    A[0].set_grid(*dims[0])
+    R, P = [], []
+    for l in (0, 1):
+        P.append(F.SparseMatOp.from_scipy(ctx, trilinear(dims[l])))
+        R.append(F.transpose(P[l]))
+        A.append(F.galerkin_rap(R[l], A[l], P[l]))
+        A[l + 1].set_grid(*dims[l + 1])
+    mg = F.Multigrid(A[0], F.new_jacobi(A[0], 0.66))
+    mg.add_level(A[1], F.new_jacobi(A[1], 0.66), R[0], P[0])
+    mg.add_level(A[2], F.CoarseCholesky(A[2]), R[1], P[1])
+    b = T(np.random.default_rng(11).uniform(-1, 1, A[0].nrows))
+    outs = {}
+    try:
+        for ff in (0, 1):
+            outs[ff], names = apply_with(ctx, mg, b, ff)
+            print(dims[0], "trilinear, fine_fuse", ff, names)
+            assert "fine-rr" not in names and "fine-pj" not in names, (ff, names)
+    finally:
+        fa().set_flag("fine_fuse", 1)
+    assert np.isfinite(outs[0]).all()
+    assert np.array_equal(bits(outs[1]), bits(outs[0]))
+    levels = []
+    for l in range(3):
+        lev = {"A": O.Csr.from_arrays(*A[l].dims(), *A[l].arrays()), "smoother": "chol" if l == 2 else "jacobi"}
+        if l < 2:
+            lev["R"] = O.Csr.from_arrays(*R[l].dims(), *R[l].arrays())
+            lev["P"] = O.Csr.from_arrays(*P[l].dims(), *P[l].arrays())
+        levels.append(lev)
+    zref = O.Multigrid(levels).apply(H(b))
+    err = np.linalg.norm(outs[1] - zref) / np.linalg.norm(zref)
+    print("trilinear V-cycle rel err vs oracle", err)
+    assert err <= 1e-11

@@ -999,6 +999,78 @@ amg_status amg_transpose(const amg_linop *P, amg_linop **out) {
     });
 }
 
+// the values of a CSR handle changed in place: its SpMV storage and cached pieces follow
+static void csr_values_changed(CsrOp &c) {
+    c.diag_.release();
+    c.transpose_.reset();
+    csr_finalize(c.m, &c.m.seg_rows);
+}
+
+amg_status amg_spgemm_refill(const amg_linop *A, const amg_linop *B, amg_linop *C) {
+    return guard([&] {
+        auto a = need_csr(A), b = need_csr(B), c = need_csr(C);
+        FAMG_REQUIRE(a->ctx == b->ctx && a->ctx == c->ctx, AMG_ERR_INVALID, "operands on different contexts");
+        FAMG_REQUIRE(c != a && c != b, AMG_ERR_INVALID, "C must not be one of the factors");
+        a->ctx->set_device();
+        spgemm_refill(a->m, b->m, c->m);
+        csr_values_changed(*c);
+    });
+}
+
+amg_status amg_transpose_perm(const amg_linop *P, const amg_linop *R, int32_t *perm) {
+    return guard([&] {
+        auto p = need_csr(P), r = need_csr(R);
+        FAMG_REQUIRE(perm, AMG_ERR_INVALID, "null output");
+        FAMG_REQUIRE(p->ctx == r->ctx, AMG_ERR_INVALID, "operands on different contexts");
+        p->ctx->set_device();
+        DevBuf<int32_t> d(std::max<int64_t>(1, p->m.nnz));
+        transpose_perm(p->m, r->m, d.get());
+        if (p->m.nnz)
+            FAMG_CHECK_HIP(hipMemcpy(perm, d.get(), p->m.nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+    });
+}
+
+amg_status amg_transpose_refill(const amg_linop *P, amg_linop *R, const int32_t *perm) {
+    return guard([&] {
+        auto p = need_csr(P), r = need_csr(R);
+        FAMG_REQUIRE(perm, AMG_ERR_INVALID, "null permutation");
+        FAMG_REQUIRE(p->ctx == r->ctx, AMG_ERR_INVALID, "operands on different contexts");
+        FAMG_REQUIRE(p != r, AMG_ERR_INVALID, "R must not be P");
+        p->ctx->set_device();
+        DevBuf<int32_t> d(std::max<int64_t>(1, p->m.nnz));
+        if (p->m.nnz)
+            FAMG_CHECK_HIP(hipMemcpy(d.get(), perm, p->m.nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+        transpose_refill(p->m, r->m, d.get());
+        csr_values_changed(*r);
+    });
+}
+
+amg_status amg_sa_refresh(amg_linop *mg, amg_linop *A_new, const double *near_null, int64_t ld, int64_t k,
+                          int64_t *info8) {
+    return guard([&] {
+        need(mg);
+        auto m = std::dynamic_pointer_cast<MultigridOp>(mg->op);
+        FAMG_REQUIRE(m && m->sa_rec, AMG_ERR_UNSUPPORTED,
+                     "amg_sa_refresh: only a multigrid that amg_sa_build made can be refreshed");
+        auto a = need_csr(A_new);
+        FAMG_REQUIRE(near_null, AMG_ERR_INVALID, "null near-null space");
+        a->ctx->set_device();
+        sa_refresh(*m, a, near_null, ld, k, info8);
+    });
+}
+
+amg_status amg_sa_level_aggregates(const amg_linop *mg, int64_t level, int64_t *agg_of, int64_t *naggs) {
+    return guard([&] {
+        auto m = need_mg(mg);
+        FAMG_REQUIRE(m->sa_rec, AMG_ERR_INVALID, "the multigrid keeps no amg_sa_build record");
+        FAMG_REQUIRE(level >= 0 && level < (int64_t)m->sa_rec->aggs.size(), AMG_ERR_INVALID, "level out of range");
+        FAMG_REQUIRE(agg_of || naggs, AMG_ERR_INVALID, "null outputs");
+        const auto &agg = m->sa_rec->aggs[level];
+        if (agg_of) std::copy(agg.begin(), agg.end(), agg_of);
+        if (naggs) *naggs = m->sa_rec->naggs[level];
+    });
+}
+
 amg_status amg_galerkin_rap(const amg_linop *R, const amg_linop *A, const amg_linop *P, amg_linop **out) {
     return guard([&] {
         FAMG_REQUIRE(out, AMG_ERR_INVALID, "null output");

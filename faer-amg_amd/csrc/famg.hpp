@@ -609,9 +609,12 @@ struct SaLevelInfo {
     int64_t n, block_size, nodes, aggregates, strength_edges, on_device = 0, host_reason = 0, longest_ball = 0;
 };
 
+struct SaRecord;  // what sa_refresh needs of the build (below, with SaConfig)
+
 struct MultigridOp : LinOp {
     std::vector<MgLevel> levels;
     std::vector<SaLevelInfo> sa_levels;  // sa_build's record, one entry per coarsening step
+    std::shared_ptr<SaRecord> sa_rec;    // sa_build only: config and aggregates, later the frozen patterns
     int64_t mu = 1, steps = 1;
     bool use_graph = true;
     bool sgs_residual_form = false;  // true: literal smooth() order (residual SpMV + SGS(r))
@@ -637,6 +640,11 @@ struct MultigridOp : LinOp {
     // launch records of one block cycle of k columns (eager, recorder on)
     std::vector<LaunchRec> block_plan(int64_t k);
     void add_level(LinOpPtr A, LinOpPtr S, LinOpPtr R, LinOpPtr P);
+    // sa_refresh's commit: every level's operators replaced at once (R, P: one per
+    // coarsening step), under mtx.  The renumbered copies are dropped, the workspaces'
+    // value-derived parts, the graphs and the dense tail are rebuilt at the next apply.
+    void install_operators(const std::vector<LinOpPtr> &As, const std::vector<LinOpPtr> &Ss,
+                           const std::vector<LinOpPtr> &Rs, const std::vector<LinOpPtr> &Ps);
     void ensure_workspace();
     void invalidate_graphs();
     ~MultigridOp() override;
@@ -955,6 +963,9 @@ CsrPtr sa_tentative_block(Ctx *ctx, int64_t nnodes, int64_t bs, const int64_t *a
                           const double *nn, int64_t ld, int64_t k, int64_t cd, double *coarse_nn);
 // block_jacobi P smoothing (interpolation/mod.rs:963-1028)
 CsrPtr block_jacobi_smooth(CsrOp &A, const CsrOp &P, int64_t bs, double omega);
+// its left factor -omega D^-1 (D = A's bs x bs diagonal blocks) as a CSR of full blocks;
+// AMG_ERR_NOT_SPD for a block with an eigenvalue <= 1e-6
+CsrPtr block_jacobi_dinv(CsrOp &A, int64_t bs, double omega);
 // create_weights (examples/amg/main.rs:571-580): w_c = 1 / (v_c^T A v_c), near-null on the host
 std::vector<double> default_weights(CsrOp &A, const double *nn, int64_t ld, int64_t k);
 // coarse near-null post-processing for k columns (hierarchy.rs:219-228)
@@ -968,6 +979,46 @@ struct SaConfig {
 };
 std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn, int64_t ld, int64_t k,
                                       const double *weights, const SaConfig &cfg, std::vector<SaLevelInfo> *info);
+// the smoother cfg names for level operator M (agg / naggs / bs: the level's aggregates, smoother 3)
+LinOpPtr sa_make_smoother(const SaConfig &cfg, const CsrPtr &M, const int64_t *agg, int64_t naggs, int64_t bs);
+
+// ------------------------------------------- SA numeric refresh (refresh.hip)
+
+// C's values = A B on C's given pattern (rows' columns ascending): every entry from 0.0,
+// fma(a_e, b, acc) in ascending order of the entries e of A's row -- spgemm's values
+// bit for bit; entries of C outside the product end 0.0.  AMG_ERR_INVALID (C's values
+// then undefined, nothing written outside them) if a product column is missing from C.
+// C is not finalized.
+void spgemm_refill(const GpuCsr &A, const GpuCsr &B, GpuCsr &C);
+// perm (device, P.nnz entries): entry q of R = P^T holds entry perm[q] of P; R's pattern
+// must be P's transpose with ascending columns (AMG_ERR_INVALID otherwise)
+void transpose_perm(const GpuCsr &P, const GpuCsr &R, int32_t *perm);
+// R.val[q] = P.val[perm[q]]; AMG_ERR_INVALID for an entry of perm outside P.  R is not finalized.
+void transpose_refill(const GpuCsr &P, GpuCsr &R, const int32_t *perm);
+// What a hierarchy of sa_build keeps for sa_refresh: the config, the candidate count
+// and every coarsening step's aggregates (host); after the first refresh the patterns
+// the symbolic passes produced (device, no values) and the transpose permutations.
+struct SaRefreshPatterns {
+    struct Step {
+        std::vector<GpuCsr> ap, s;  // per smoothing step: A P, and (block size > 1) D^-1 (A P)
+        GpuCsr rap_ap;              // A P of the Galerkin product
+        DevBuf<int32_t> perm;       // R = P^T as a gather
+    };
+    std::vector<Step> steps;
+    int64_t bytes = 0;
+};
+struct SaRecord {
+    SaConfig cfg;
+    int64_t k = 0;
+    std::vector<std::vector<int64_t>> aggs;  // per coarsening step: aggregate of every node
+    std::vector<int64_t> naggs, bss;         // bss: block size of every level
+    std::shared_ptr<SaRefreshPatterns> pat;  // null until the first refresh
+};
+// The hierarchy sa_build would make for A (the build's pattern, new values) and nn had
+// strength and aggregation returned the recorded aggregates; mg changes only if every
+// stage succeeds.  info8 = {recorded (1) or reused (0) the patterns, device bytes of the
+// record, levels, coarsening steps, 0...}.
+void sa_refresh(MultigridOp &mg, const CsrPtr &A, const double *nn, int64_t ld, int64_t k, int64_t *info8);
 
 // ------------------------------------------- near-null search (nearnull.hip)
 

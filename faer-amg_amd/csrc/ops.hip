@@ -465,6 +465,37 @@ void MultigridOp::add_level(LinOpPtr A, LinOpPtr S, LinOpPtr R, LinOpPtr P) {
     invalidate_graphs();
 }
 
+void MultigridOp::install_operators(const std::vector<LinOpPtr> &As, const std::vector<LinOpPtr> &Ss,
+                                    const std::vector<LinOpPtr> &Rs, const std::vector<LinOpPtr> &Ps) {
+    std::lock_guard<std::mutex> lk(mtx);
+    const size_t NL = levels.size();
+    FAMG_REQUIRE(As.size() == NL && Ss.size() == NL && Rs.size() + 1 == NL && Ps.size() + 1 == NL, AMG_ERR_INVALID,
+                 "install_operators: one A and S per level, one R and P per coarsening step");
+    for (size_t l = 0; l < NL; l++) {
+        FAMG_REQUIRE(As[l] && Ss[l] && (l + 1 == NL || (Rs[l] && Ps[l])), AMG_ERR_INVALID,
+                     "install_operators: null operator");
+        FAMG_REQUIRE(As[l]->nrows == levels[l].origA()->nrows && As[l]->ncols == As[l]->nrows &&
+                         Ss[l]->nrows == As[l]->nrows,
+                     AMG_ERR_DIM, "install_operators: a level changes size");
+    }
+    undo_reorder();  // drops the renumbered copies and every graph; renumbered again at the next apply
+    for (size_t l = 0; l < NL; l++) {
+        levels[l].A = As[l];
+        levels[l].S = Ss[l];
+        levels[l].R = l + 1 < NL ? Rs[l] : nullptr;
+        levels[l].P = l + 1 < NL ? Ps[l] : nullptr;
+    }
+    for (size_t l = 0; l + 1 < NL; l++) {  // as add_level does for a level it appends
+        auto *Af = dynamic_cast<CsrOp *>(levels[l].A.get());
+        auto *Ac = dynamic_cast<CsrOp *>(levels[l + 1].A.get());
+        auto *Rc = dynamic_cast<CsrOp *>(levels[l].R.get());
+        auto *Pc = dynamic_cast<CsrOp *>(levels[l].P.get());
+        if (Af && Ac && Rc && Pc) attach_box_transfers(Af->m, Ac->m, Rc->m, Pc->m);
+    }
+    workspace_ready_ = false;  // the new Jacobi diagonals get their codes before any capture
+    invalidate_graphs();       // and the dense tail is rebuilt from the new operators
+}
+
 void MultigridOp::ensure_workspace() {
     if (workspace_ready_) return;
     if (!reorder_done_) reorder_levels();

@@ -506,10 +506,9 @@ static bool block_inverse_eig(int64_t bs, const double *lower_rowmajor, double *
     return true;
 }
 
-// block_jacobi (interpolation/mod.rs:963-1028): P_s = (-omega D^-1) (A P) + P,
-// D = the bs x bs diagonal blocks of A.
-CsrPtr block_jacobi_smooth(CsrOp &A, const CsrOp &P, int64_t bs, double omega) {
-    FAMG_REQUIRE(A.nrows == A.ncols && A.ncols == P.nrows, AMG_ERR_DIM, "block_jacobi dims");
+// -omega D^-1 of block_jacobi as a CSR of full bs x bs blocks (D = A's diagonal blocks)
+CsrPtr block_jacobi_dinv(CsrOp &A, int64_t bs, double omega) {
+    FAMG_REQUIRE(A.nrows == A.ncols, AMG_ERR_DIM, "block_jacobi dims");
     FAMG_REQUIRE(bs >= 1 && A.nrows % bs == 0, AMG_ERR_DIM, "block_jacobi: block size must divide n");
     Ctx *ctx = A.ctx;
     hipStream_t s = ctx->stream;
@@ -543,15 +542,24 @@ CsrPtr block_jacobi_smooth(CsrOp &A, const CsrOp &P, int64_t bs, double omega) {
     for (int64_t i = 0; i <= n; i++) rp[i] = i * bs;
     auto Dinv = make_csr(ctx);
     csr_from_host(Dinv->m, ctx, n, n, rp.data(), col.data(), val.data());
+    Dinv->nrows = Dinv->ncols = n;
+    return Dinv;
+}
+
+// block_jacobi (interpolation/mod.rs:963-1028): P_s = (-omega D^-1) (A P) + P,
+// D = the bs x bs diagonal blocks of A.
+CsrPtr block_jacobi_smooth(CsrOp &A, const CsrOp &P, int64_t bs, double omega) {
+    FAMG_REQUIRE(A.nrows == A.ncols && A.ncols == P.nrows, AMG_ERR_DIM, "block_jacobi dims");
+    auto Dinv = block_jacobi_dinv(A, bs, omega);
     GpuCsr AP;
     spgemm(A.m, P.m, AP, false);
     GpuCsr S;
     spgemm(Dinv->m, AP, S, false);
     csr_add_into(S, P.m);
     csr_finalize(S);
-    auto out = make_csr(ctx);
+    auto out = make_csr(A.ctx);
     out->m = std::move(S);
-    out->nrows = n;
+    out->nrows = A.nrows;
     out->ncols = P.ncols;
     return out;
 }
@@ -643,6 +651,27 @@ std::vector<double> default_weights(CsrOp &A, const double *nn, int64_t ld, int6
         w[c] = 1.0 / vtav;
     }
     return w;
+}
+
+LinOpPtr sa_make_smoother(const SaConfig &cfg, const CsrPtr &M, const int64_t *agg, int64_t naggs, int64_t bs) {
+    switch (cfg.smoother) {
+    case 0: return make_jacobi(*M, cfg.omega);
+    case 1: return make_l1(*M);
+    case 2: {
+        std::vector<int32_t> colors;
+        const int64_t ncol = greedy_coloring(M->m, colors);
+        if (ncol <= SGS_MAX_COLORS) return make_sgs(M, colors.data(), false);
+        return make_l1(*M);
+    }
+    case 3:  // BlockSmoother over the level's aggregates (block_smoothers.rs)
+        return make_block_smoother(*M, agg, naggs, bs);
+    case 4: {  // Chebyshev (cheby.hip), its other parameters at their defaults
+        ChebyConfig cc;
+        if (cfg.chebyshev_steps > 0) cc.steps = cfg.chebyshev_steps;
+        return make_chebyshev(M, cc);
+    }
+    default: fail(AMG_ERR_INVALID, "unknown smoother kind");
+    }
 }
 
 std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int64_t ld, int64_t k,
@@ -746,24 +775,8 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
         level++;
     }
     auto make_smoother = [&](const CsrPtr &M, size_t l) -> LinOpPtr {
-        switch (cfg.smoother) {
-        case 0: return make_jacobi(*M, cfg.omega);
-        case 1: return make_l1(*M);
-        case 2: {
-            std::vector<int32_t> colors;
-            const int64_t ncol = greedy_coloring(M->m, colors);
-            if (ncol <= SGS_MAX_COLORS) return make_sgs(M, colors.data(), false);
-            return make_l1(*M);
-        }
-        case 3:  // BlockSmoother over the level's aggregates (block_smoothers.rs)
-            return make_block_smoother(*M, aggs[l].data(), naggs[l], bss[l]);
-        case 4: {  // Chebyshev (cheby.hip), its other parameters at their defaults
-            ChebyConfig cc;
-            if (cfg.chebyshev_steps > 0) cc.steps = cfg.chebyshev_steps;
-            return make_chebyshev(M, cc);
-        }
-        default: fail(AMG_ERR_INVALID, "unknown smoother kind");
-        }
+        const bool has = l < aggs.size();  // (only levels with aggregates get a smoother)
+        return sa_make_smoother(cfg, M, has ? aggs[l].data() : nullptr, has ? naggs[l] : 0, bss[l]);
     };
     auto mg = std::make_shared<MultigridOp>();
     mg->ctx = ctx;
@@ -779,6 +792,14 @@ std::shared_ptr<MultigridOp> sa_build(const CsrPtr &A, const double *nn_in, int6
         mg->add_level(As[l], S, Rs[l - 1], Ps[l - 1]);
     }
     if (clk.on) fprintf(stderr, "famg sa smoothers: levels %lld ms: smoothers %.3f\n", (long long)As.size(), clk.lap());
+    // what sa_refresh (refresh.hip) rebuilds the hierarchy from: host memory only
+    auto rec = std::make_shared<SaRecord>();
+    rec->cfg = cfg;
+    rec->k = k;
+    rec->aggs = std::move(aggs);
+    rec->naggs = std::move(naggs);
+    rec->bss = std::move(bss);
+    mg->sa_rec = std::move(rec);
     return mg;
 }
 

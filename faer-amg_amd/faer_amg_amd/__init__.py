@@ -186,6 +186,11 @@ SIGNATURES = {
     "amg_pattern_ball_device": (i32, [vp, i64, P(vp)]),
     "amg_strength_graph_device_depth": (i32, [vp, vp, i64, i64, vp, i64, i64, C.c_int, i64, P(vp), vp]),
     "amg_sa_level_info": (i32, [vp, i64, vp]),
+    "amg_sa_level_aggregates": (i32, [vp, i64, vp, P(i64)]),
+    "amg_sa_refresh": (i32, [vp, vp, vp, i64, i64, vp]),
+    "amg_spgemm_refill": (i32, [vp, vp, vp]),
+    "amg_transpose_perm": (i32, [vp, vp, vp]),
+    "amg_transpose_refill": (i32, [vp, vp, vp]),
     "amg_partitioner_config_default": (i32, [vp]),
     "amg_partition_modularity": (i32, [vp, vp, vp, P(i64), vp]),
     "amg_partition_modularity_device": (i32, [vp, vp, vp, P(i64), vp]),
@@ -843,6 +848,27 @@ class Multigrid(LinOp):
         _ck(_lib.amg_sa_level_info(self.h, int(level), out.ctypes.data_as(vp)))
         return tuple(int(v) for v in out)
 
+    def sa_aggregates(self, level):
+        """amg_sa_level_aggregates: (agg_of, naggs) smoothed_aggregation recorded for
+        coarsening step `level` -- the aggregate of every node (int64) and their count."""
+        nodes = self.sa_level_info(level)[2]
+        agg = np.zeros(nodes, np.int64)
+        na = i64()
+        _ck(_lib.amg_sa_level_aggregates(self.h, int(level), agg.ctypes.data_as(vp), C.byref(na)))
+        return agg, na.value
+
+    def refresh(self, A_new, near_null):
+        """amg_sa_refresh: rebuild this smoothed_aggregation hierarchy for A_new (the
+        build's sparsity pattern, new values) and near_null (n x k, the build's k) on the
+        recorded aggregates.  The first call records the product patterns, later ones are
+        numeric only; a failure leaves the hierarchy as it was.  Level handles taken
+        before keep the old operators.  Returns {recorded, record_bytes, levels, steps}."""
+        nn = _colmajor_host(near_null, A_new.nrows)
+        out = np.zeros(8, np.int64)
+        _ck(_lib.amg_sa_refresh(self.h, A_new.h, nn.ctypes.data_as(vp), nn.shape[0], nn.shape[1],
+                                out.ctypes.data_as(vp)))
+        return {"recorded": bool(out[0]), "record_bytes": int(out[1]), "levels": int(out[2]), "steps": int(out[3])}
+
     def level(self, l):
         """(A, S, R, P) handles of level l (R, P None on the coarsest)."""
         a, s, r, p = vp(), vp(), vp(), vp()
@@ -865,6 +891,30 @@ def transpose(P_):
     h = vp()
     _ck(_lib.amg_transpose(P_.h, C.byref(h)))
     return SparseMatOp(h, P_.ctx)
+
+
+def spgemm_refill(A, B, C_):
+    """amg_spgemm_refill: overwrite C_'s values with A B on C_'s given pattern (spgemm's
+    values bit for bit, 0.0 outside the product); AmgError (invalid) if a product column
+    is missing from C_."""
+    _ck(_lib.amg_spgemm_refill(A.h, B.h, C_.h))
+    return C_
+
+
+def transpose_perm(P_, R):
+    """amg_transpose_perm: int32 perm with R.val[q] = P_.val[perm[q]] for R = P_^T."""
+    perm = np.zeros(P_.nnz, np.int32)
+    _ck(_lib.amg_transpose_perm(P_.h, R.h, perm.ctypes.data_as(vp)))
+    return perm
+
+
+def transpose_refill(P_, R, perm):
+    """amg_transpose_refill: overwrite R's values with P_'s through perm (transpose_perm)."""
+    perm = np.ascontiguousarray(perm, np.int32)
+    if perm.shape != (P_.nnz,):
+        raise ValueError("perm must have one entry per stored entry of P")
+    _ck(_lib.amg_transpose_refill(P_.h, R.h, perm.ctypes.data_as(vp)))
+    return R
 
 
 def galerkin_rap(R, A, P_):

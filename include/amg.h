@@ -638,6 +638,58 @@ amg_status amg_strength_graph_device_depth(const amg_linop *A, const double *nea
  * a multigrid without such a record (built another way, or with one level), a
  * level out of range. */
 amg_status amg_sa_level_info(const amg_linop *mg, int64_t level, int64_t *out8);
+/* The aggregates amg_sa_build recorded for coarsening step `level`: agg_of (host,
+ * the step's node count of amg_sa_level_info, may be null) and *naggs (may be null,
+ * not both).  AMG_ERR_INVALID as amg_sa_level_info. */
+amg_status amg_sa_level_aggregates(const amg_linop *mg, int64_t level, int64_t *agg_of, int64_t *naggs);
+/* ---- numeric re-setup: the same sparsity pattern, new values ------------------
+ * amg_sa_refresh rebuilds the hierarchy of `mg` -- a multigrid amg_sa_build made;
+ * any other one (box, classical, hand-composed, adaptive, distributed):
+ * AMG_ERR_UNSUPPORTED -- for A_new, a CSR handle on the same context whose row
+ * pointers and column indices equal the build's fine operator (compared on the
+ * device; AMG_ERR_INVALID if they differ), and near_null (host, n x k column-major,
+ * ld >= n, the build's k: AMG_ERR_INVALID otherwise).  Weights are not taken: they
+ * only feed the strength graph.  The result is the hierarchy amg_sa_build would
+ * make for A_new had strength and aggregation returned the recorded aggregates:
+ * per coarsening step the tentative P of the frozen aggregates and the current
+ * near-null space, `smoothing_steps` of P smoothing, R = P^T, A_c = R (A P), the
+ * coarse near-null post-processing; then the configured smoothers and the coarsest
+ * Cholesky factor.  mu, steps, graph, reorder and every amg_multigrid_set_option
+ * value stay as set.
+ *   The first refresh of a hierarchy runs the symbolic passes once and records, on
+ * the device, the pattern of every A P and D^-1 (A P) intermediate and the
+ * transpose permutations (info8[1] bytes, held until the multigrid is destroyed);
+ * later refreshes are numeric only.  amg_sa_build itself keeps only its config and
+ * the host aggregates.
+ *   A refresh that fails at any stage (AMG_ERR_INVALID above, AMG_ERR_NOT_SPD from
+ * a diagonal block or the coarsest factor, ...) leaves the multigrid exactly as
+ * it was.  On success the next apply rebuilds the renumbered copies, the diagonal
+ * codes, the dense tail and every captured graph: no cycle replays a graph
+ * captured before the refresh.
+ *   Aliasing: the refresh installs new operators.  The multigrid keeps a reference
+ * to A_new as its fine operator (destroying the caller's handle is fine; changing
+ * its values is not), and handles obtained earlier through amg_multigrid_get_level
+ * keep the operators of the hierarchy they were taken from -- they do not see the
+ * new values; ask again after the refresh.
+ *   info8 (may be null) = {1 if this call recorded the patterns, 0 if it reused
+ * them; device bytes of the record; levels; coarsening steps; 0, 0, 0, 0}. */
+amg_status amg_sa_refresh(amg_linop *mg, amg_linop *A_new, const double *near_null, int64_t ld, int64_t k,
+                          int64_t *info8);
+/* The two kernels of a later refresh on their own.
+ * amg_spgemm_refill overwrites C's values with A * B on C's given pattern (every
+ * row's columns ascending, as amg_spgemm returns them): amg_spgemm's values bit
+ * for bit, 0.0 in entries of C outside the product.  AMG_ERR_INVALID if a column of
+ * the product is missing from C (reported through a device flag; C's values are
+ * then undefined and nothing outside them is written) or C is A or B; AMG_ERR_DIM
+ * for mismatched shapes.
+ * amg_transpose_perm: perm (host, nnz entries) such that entry q of R = P^T is
+ * entry perm[q] of P, for an R with the pattern amg_transpose(P) gives
+ * (AMG_ERR_INVALID for another pattern, AMG_ERR_DIM for another shape).
+ * amg_transpose_refill: R.val[q] = P.val[perm[q]] (AMG_ERR_INVALID for an entry of
+ * perm outside [0, nnz)).  Both refills rebuild the SpMV storage of what they wrote. */
+amg_status amg_spgemm_refill(const amg_linop *A, const amg_linop *B, amg_linop *C);
+amg_status amg_transpose_perm(const amg_linop *P, const amg_linop *R, int32_t *perm);
+amg_status amg_transpose_refill(const amg_linop *P, amg_linop *R, const int32_t *perm);
 /* amg_aggregate_mis (maximal_independent_set, partitioners/mod.rs:395-423) of a
  * square CSR handle -- a result of amg_strength_graph_device or a graph uploaded
  * with amg_csr_create: exactly the host's agg_of (host, n entries) and *naggs.

@@ -74,13 +74,16 @@ def row_sums(rp, col, val, x):
 
 
 class Case:
-    """A CSR operator with its vectors, the reference of every mode and its tolerance."""
+    """A CSR operator with its vectors, the reference of every mode and its tolerance.
+    ncols (default n: square) sizes x; the Jacobi epilogue reads x_i of every row, so x
+    of an operator with more rows than columns is drawn n long."""
 
-    def __init__(self, name, n, rp, col, val, seed, forced=False, expect=None):
+    def __init__(self, name, n, rp, col, val, seed, forced=False, expect=None, ncols=None):
         self.name, self.n, self.forced, self.expect = name, n, forced, expect or {}
+        self.ncols = n if ncols is None else ncols
         self.rp, self.col, self.val = rp.astype(np.int64), col.astype(np.int64), val.astype(np.float64)
         rng = np.random.default_rng(seed)
-        self.x, self.b, self.y0 = (rng.uniform(-1, 1, n) for _ in range(3))
+        self.x, self.b, self.y0 = (rng.uniform(-1, 1, m) for m in (max(n, self.ncols), n, n))
         self.d = rng.uniform(0.1, 0.2, n)
         self.lens = np.diff(self.rp)
         self._ref = None
@@ -94,7 +97,7 @@ class Case:
         """{mode: (ref, tol)} in np.longdouble; computed once."""
         if self._ref is None:
             s, S = row_sums(self.rp, self.col, self.val, self.x)
-            x, b, y0, d = (v.astype(LD) for v in (self.x, self.b, self.y0, self.d))
+            x, b, y0, d = (v.astype(LD) for v in (self.x[:self.n], self.b, self.y0, self.d))
             E = 2 * self.lens.astype(LD) * LD(U) * S
             tiny = LD(1e-300)
             ref = {"set": s, "add": y0 + s, "resid": b - s, "jacobi": x + d * (b - s)}
@@ -108,7 +111,7 @@ class Case:
     def empty_exact(self, mode):
         """What an empty row holds, rounded as the kernel rounds it (acc = +0.0)."""
         e = self.lens == 0
-        x, b, y0, d = self.x[e], self.b[e], self.y0[e], self.d[e]
+        x, b, y0, d = self.x[:self.n][e], self.b[e], self.y0[e], self.d[e]
         return {"set": np.zeros(int(e.sum())), "add": y0 + 0.0, "resid": b - 0.0, "jacobi": x + d * (b - 0.0)}[mode]
 
     def check(self, mode, y):
@@ -127,7 +130,7 @@ class Case:
         try:
             if self.forced:
                 F.set_spmv_format("vector")
-            return F.SparseMatOp.from_arrays(ctx, self.n, self.n, self.rp, self.col, self.val)
+            return F.SparseMatOp.from_arrays(ctx, self.n, self.ncols, self.rp, self.col, self.val)
         finally:
             F.set_spmv_format("auto")
 
@@ -136,7 +139,7 @@ def check_csr(c):
     """Sorted, in-range CSR with strictly ascending columns in every row."""
     assert c.rp[0] == 0 and len(c.rp) == c.n + 1 and np.all(np.diff(c.rp) >= 0)
     assert len(c.col) == len(c.val) == c.nnz
-    assert c.col.min() >= 0 and c.col.max() < c.n
+    assert c.col.min() >= 0 and c.col.max() < c.ncols
     inner = np.ones(c.nnz, bool)
     inner[c.rp[:-1][c.lens > 0]] = False  # the first entry of a row has no predecessor in it
     assert np.all(np.diff(c.col)[inner[1:]] > 0)
